@@ -42,6 +42,7 @@ if ROOT not in sys.path:
 # multi-process GPU work on this pool: the host driver only supports dmabuf IPC (RCCL / cross-process tensors fail otherwise)
 os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn.functional as tf
@@ -328,6 +329,31 @@ def run_variant(config, extra_args=(), env=None, steps=20, warmup=5, timeout=300
         return {'error': f'{type(exc).__name__}: {str(exc)[:200]}'}
 
 
+DUMP_CAP_ELEMENTS = 4 << 20          # per array: 16 MB of float32, so the three arrays stay under 64 MB
+
+
+def dump_outputs(directory, model, loss):
+    """--dump-outputs: what the last timed step handed its caller, for comparing two builds output for output.
+      loss.npy    the step's loss (shape (1,))
+      grads.npy   every parameter's gradient of that step, flattened and concatenated in named_parameters() order
+      params.npy  the parameters after that step's optimizer update, same layout
+    float32.  An array longer than DUMP_CAP_ELEMENTS is cut to a fixed sample: the same sorted positions, drawn by a seeded
+    generator from its length alone, on every run."""
+    os.makedirs(directory, exist_ok=True)
+    named = list(model.named_parameters())
+    arrays = {
+        'loss': loss.detach().float().reshape(1),
+        'grads': torch.cat([p.grad.detach().float().reshape(-1) for _, p in named if p.grad is not None]),
+        'params': torch.cat([p.detach().float().reshape(-1) for _, p in named]),
+    }
+    for name, t in arrays.items():
+        t = t.cpu()
+        if t.numel() > DUMP_CAP_ELEMENTS:
+            keep = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_CAP_ELEMENTS].sort().values
+            t = t[keep]
+        np.save(os.path.join(directory, f'{name}.npy'), t.numpy())
+
+
 def _dry_rank(rank, world, port, queue):
     """One rank of `--dry-collectives`: gloo over CPU tensors, a small pure-torch network with several gradient buckets, the two
     sequencings pvcnn_amd/graph.py captures on the GPU issued eagerly (capture=False) -- the collectives are the REAL ones of
@@ -468,7 +494,12 @@ def main():
                     help='no GPU needed: run the N-rank step SEQUENCING (both orderings of pvcnn_amd/graph.py\'s multi-rank branch, issued eagerly) '
                          'on a reduced-width network over gloo / CPU tensors with the CPU oracle as native backend and check it against the '
                          'single-process step on the concatenated batch; prints one JSON line (not a performance figure)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step handed its caller (loss, every parameter gradient, the '
+                         'parameters after the optimizer step) as DIR/<name>.npy, float32, at most 64 MB in all (see dump_outputs)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.dry_collectives:
         report = dry_collectives(max(2, args.gpus))
@@ -630,6 +661,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     final_loss = float(loss.detach())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, loss)     # before the eager steps below move the parameters on
 
     # ---- the step's collectives alone (all buckets, back to back, nothing to overlap with): what NOT overlapping them would cost ----
     comm_us = None

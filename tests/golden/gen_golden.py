@@ -13,6 +13,7 @@ Run:  python tests/golden/gen_golden.py      (needs /root/reference; rewrites th
 """
 import importlib
 import os
+import subprocess
 import sys
 import types
 
@@ -107,5 +108,14 @@ def main():
         print(name, os.path.getsize(os.path.join(HERE, f'{name}.pt')), 'bytes')
 
 
+def record_ref_kernels():
+    """tests/golden/ref_kernels.pt.xz: the reference kernels' outputs for every call tests/test_oracle_vs_ref.py makes (the reference
+    side of those tests where oracle/_ref cannot be built)."""
+    build_ref.main()
+    subprocess.check_call([sys.executable, '-m', 'pytest', '-q', '-p', 'no:cacheprovider', os.path.join('tests', 'test_oracle_vs_ref.py')],
+                          cwd=ROOT, env=dict(os.environ, PVCNN_RECORD_REF=os.path.join(HERE, 'ref_kernels.pt.xz')))
+
+
 if __name__ == '__main__':
     main()
+    record_ref_kernels()

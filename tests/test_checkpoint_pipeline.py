@@ -37,7 +37,7 @@ def test_reference_style_checkpoint_round_trip(tmp_path, oracle_seam):
     # wrapped target (DataParallel keeps the prefix) and the save direction
     wrapped = torch.nn.DataParallel(workload.PVCNN(13, 6, width_multiplier=0.125))
     load_reference_checkpoint(str(path), wrapped)
-    assert torch.equal(wrapped.module.classifier[-1].weight, src.classifier[-1].weight)
+    assert torch.equal(wrapped.module.classifier[-1].weight.cpu(), src.classifier[-1].weight)    # (DataParallel moves it to a GPU if there is one)
     out = tmp_path / 'mine.pth.tar'
     save_reference_checkpoint(str(out), dst, epoch=3)
     blob = torch.load(out, weights_only=False)

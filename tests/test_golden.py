@@ -51,7 +51,7 @@ def check_native(be, dev):
     assert torch.equal(be.furthest_point_sampling(_to(g['points'], dev), g['m']).cpu(), g['idx'])
 
 
-def check_modules(dev, atol):
+def check_modules(dev, atol, net_atol=None):
     from pvcnn_amd import workload
     from pvcnn_amd.modules import PVConv
     g = load('pvconv_eval')
@@ -68,7 +68,8 @@ def check_modules(dev, atol):
     net = net.to(dev).eval()
     with torch.no_grad():
         logits = net(g['x'].to(dev))
-    assert torch.allclose(logits.cpu(), g['logits'], atol=atol, rtol=atol), ((logits.cpu() - g['logits']).abs() / (1 + g['logits'].abs())).max().item()
+    net_atol = atol if net_atol is None else net_atol
+    assert torch.allclose(logits.cpu(), g['logits'], atol=net_atol, rtol=net_atol), ((logits.cpu() - g['logits']).abs() / (1 + g['logits'].abs())).max().item()
 
 
 def test_oracle_reproduces_reference_vectors(oracle):
@@ -76,7 +77,10 @@ def test_oracle_reproduces_reference_vectors(oracle):
 
 
 def test_modules_reproduce_reference_vectors_cpu(oracle_seam):
-    check_modules('cpu', atol=0)       # same torch-CPU Conv3d/BN + bit-exact native ops => identical
+    # the PVConv layer: same torch-CPU Conv3d/BN + bit-exact native ops => identical.  The whole network adds torch-CPU GEMMs whose
+    # kernels the math library picks by host CPU: on a host other than the one that wrote the vectors they sum in another order
+    # (another host read 5.2e-8 * (1 + |reference|)), so there the bar is fp32 rounding, 1e-6 -- below the GPU test's 2e-6
+    check_modules('cpu', atol=0, net_atol=1e-6)
 
 
 @pytest.mark.gpu
