@@ -47,7 +47,7 @@ extern "C" {
 #define PVCNN_API
 #endif
 
-#define PVCNN_ABI_VERSION 12
+#define PVCNN_ABI_VERSION 13
 #define PVCNN_OK 0
 #define PVCNN_ERR_INVALID_ARGUMENT (-1)
 
@@ -564,6 +564,53 @@ PVCNN_API int pvcnn_dense_bn_relu_bwd(const float *x, const float *grad_y, const
  * schedule (train.py:121-122: scheduler.step()) reaches launches that were captured into a hipGraph. */
 PVCNN_API int pvcnn_adam_step(float *p, const float *g, float *m, float *v, size_t n, float *step, const float *hyper, int inc_step,
                     void *stream);
+
+/* ---- (ABI v13) evaluation on the device (csrc/evaluate.hip): evaluate/s3dis/eval.py:139-216, evaluate/shapenet/eval.py:124-200,
+ * meters/s3dis.py, meters/shapenet.py.  Integer atomics only: every output is bitwise deterministic.  Index arrays are int64 (what
+ * the reference's numpy code holds); an index outside its range is never dereferenced (see each entry point).
+ *
+ * pvcnn_eval_tile: the reference's repeat / shuffle / tile + reshape(B*E, num_points, C).transpose in one pass,
+ *   out[b*E+e, c, j] = src[b*batch_stride + shuffled[b, e*num_points+j]*point_stride + c*chan_stride],   E = V / num_points,
+ * shuffled (B, V), out (B*E, C, num_points) fp32; element strides: a channels-last (W, maxpts, C) window block is (maxpts*C, C, 1),
+ * a channels-first (C, P) point set (0, 1, P).  An index outside [0, src_points) writes a quiet NaN.  Bit-exact (a copy). */
+PVCNN_API int pvcnn_eval_tile(const float *src, long long batch_stride, long long point_stride, long long chan_stride, long long src_points,
+                              const long long *shuffled, int B, int V, int num_points, int C, float *out, void *stream);
+/* pvcnn_vote_confidence: logits (B, C, N) -> conf (B, N) fp32, pred (B, N) int32 = F.softmax(x, 1)[:, c0:c1].max(1) with pred += c0.
+ * The class range is (c0, c1) for every cloud, or, with `ranges` non-NULL, the per-cloud int32 table ranges (B, 2) in device memory
+ * (clamped to [0, C); an empty range gives conf 0, pred -1).  Per point: m = max over all C; s = sum of expf(x_c - m) in class order;
+ * conf = expf(x_k - m) / s.  Ties go to the LOWEST k.  expf is the ocml function torch's softmax calls: only the order of torch's sum
+ * can differ. */
+PVCNN_API int pvcnn_vote_confidence(const float *logits, int B, int C, int N, int c0, int c1, const int *ranges, float *conf, int *pred,
+                                    void *stream);
+/* pvcnn_vote_merge: update_scene_predictions / update_shape_predictions reproduced exactly, without a host sync.  Vote (b, p) of
+ * conf / pred (B, V) targets t = mapping[b*map_stride + shuffled[b, p]] (mapping NULL: t = shuffled[b, p]); the result equals running,
+ * in (b, p) order, `if conf > scene_conf[t]: scene_conf[t] = conf; scene_pred[t] = pred`: the first vote that carries a point's
+ * maximum wins, and only if it is strictly greater than the stored value.  Votes with conf <= 0 or NaN never win (the state starts
+ * at 0) and are dropped, as are votes whose index or target is out of range (shuffled outside [0, map_stride) with a mapping; t outside
+ * [0, P)).  scene_conf (P) fp32 and scene_pred (P) int64 are updated in place.  workspace: pvcnn_vote_merge_workspace_bytes(P) bytes,
+ * 8-byte aligned, ZERO before the first call; every call leaves it zero again (a captured graph can replay it).  Two launches.
+ * Requires B*V < 2^32 and P < 2^31. */
+PVCNN_API size_t pvcnn_vote_merge_workspace_bytes(long long P);
+PVCNN_API int pvcnn_vote_merge(const float *conf, const int *pred, const long long *shuffled, const long long *mapping, long long map_stride,
+                               int B, int V, long long P, float *scene_conf, long long *scene_pred, void *workspace, size_t workspace_bytes,
+                               void *stream);
+/* pvcnn_seg_counts: update_stats of evaluate/s3dis/eval.py:205-213.  ADDS [seen; positive; correct] of (gt, pred), P int64 values
+ * each, into counts (3, C) int64 (accumulated: the caller zeroes it).  wrap_negative != 0 reproduces the reference's numpy indexing:
+ * a value in [-C, 0) counts for class value + C -- a point no window voted for keeps pred = -1 and is a POSITIVE OF CLASS C-1
+ * (stats[1, -1]); wrap_negative == 0: such values count nowhere.  Any other value outside [0, C) counts nowhere.  C <= 4096. */
+PVCNN_API int pvcnn_seg_counts(const long long *gt, const long long *pred, long long P, int C, int wrap_negative, long long *counts,
+                               void *stream);
+/* pvcnn_seg_meter_update: one read of logits (B, C, N) and int64 targets (B, N), argmax semantics of torch.argmax (the first maximum;
+ * a NaN wins against numbers).  B*N < 2^31, C <= 4096.
+ *   S3DIS mode (part_ranges NULL): counts (3C + 2) int64 += [seen C | positive C | correct C | numel | correct] (MeterS3DIS.update).
+ *   ShapeNet mode: part_ranges (num_part_classes, 2) int32 in device memory maps targets[b, 0] to the shape's part range [s, e),
+ *   e - s <= max_parts <= 64; the prediction is the argmax inside [s, e) plus s.  Cloud b WRITES row r = *row_cursor + b (row_cursor:
+ *   one int64 in device memory, NULL = 0) of rows (row_capacity, max_parts + 1, 2) int32: (s, e), then (intersection, union) of the
+ *   part classes s .. e-1, zeros after.  A label outside the table or a bad range writes (0, 0); a row at or beyond row_capacity is
+ *   not written (the caller advances the cursor and checks it against the capacity).  counts is unused. */
+PVCNN_API int pvcnn_seg_meter_update(const float *logits, const long long *targets, int B, int C, int N, const int *part_ranges,
+                                     int num_part_classes, int max_parts, long long *counts, int *rows, const long long *row_cursor,
+                                     long long row_capacity, void *stream);
 
 #ifdef __cplusplus
 }

@@ -16,9 +16,10 @@ import torch  # noqa: F401  (must be imported before the dlopen, see above)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB_PATH = os.path.join(_CSRC, 'libpvcnn_hip.so')
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _vp, _i, _f, _sz, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
+_ll = ctypes.c_longlong
 
 # name -> (restype, argtypes); mirrors include/pvcnn_hip.h one to one
 SIGNATURES = {
@@ -119,6 +120,12 @@ SIGNATURES = {
     'pvcnn_dense_bn_relu_bwd': (_i, [_vp] * 7 + [_i, _i, _i] + [_vp] * 6),
     'pvcnn_adam_step': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _vp]),
     'pvcnn_trilinear_devox_bwd_strided': (_i, [_vp, ctypes.c_long, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'pvcnn_eval_tile': (_i, [_vp, _ll, _ll, _ll, _ll, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'pvcnn_vote_confidence': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'pvcnn_vote_merge_workspace_bytes': (_sz, [_ll]),
+    'pvcnn_vote_merge': (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _ll, _vp, _vp, _vp, _sz, _vp]),
+    'pvcnn_seg_counts': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
+    'pvcnn_seg_meter_update': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _ll, _vp]),
 }
 
 _lib = None

@@ -1297,6 +1297,106 @@ class HipBackend:
         return (gx, gg, gb, gx_amax) if amax_seg > 0 else (gx, gg, gb)
 
 
+    # ---- evaluation (csrc/evaluate.hip, ABI v13): evaluate/{s3dis,shapenet}/eval.py and meters/{s3dis,shapenet}.py on the device --------
+    def eval_tile(self, src, shuffled, num_points, channels, strides, src_points):
+        """-> (B*E, channels, num_points) float32, the model input of the reference's repeat / shuffle / tile.  src: a contiguous float32
+        device tensor; strides = (batch, point, channel) element strides into it; src_points: points per batch item (shuffled indices
+        must lie in [0, src_points)); shuffled (B, V) int64, V % num_points == 0."""
+        _f32(src, 'src'); _dev(shuffled, 'shuffled')
+        _shape(shuffled.dtype == torch.int64 and shuffled.dim() == 2 and shuffled.is_contiguous(), 'eval_tile: shuffled (B,V) int64 expected')
+        b, v = shuffled.shape
+        np_, c, (bs, ps, cs) = int(num_points), int(channels), (int(x) for x in strides)
+        _shape(np_ > 0 and v % np_ == 0 and c > 0, 'eval_tile: V must be a multiple of num_points')
+        _shape(min(bs, ps, cs) >= 0 and (b == 0 or (b - 1) * bs + (int(src_points) - 1) * ps + (c - 1) * cs < src.numel()),
+               'eval_tile: strides reach beyond src')
+        out = torch.empty((b * (v // np_), c, np_), dtype=torch.float32, device=src.device)
+        with _Launch(src) as s:
+            _lib.check(self.lib.pvcnn_eval_tile(_p(src), bs, ps, cs, int(src_points), _p(shuffled), b, v, np_, c, _p(out), s), 'eval_tile')
+        return out
+
+    def vote_confidence(self, logits, class_range=None):
+        """logits (B, C, N) -> (conf (B, N) float32, pred (B, N) int32) = F.softmax(logits, 1)[:, c0:c1].max(1), pred + c0.
+        class_range: None (all classes), (c0, c1), or a (B, 2) int32 device tensor of per-cloud ranges."""
+        _f32(logits, 'logits')
+        _shape(logits.dim() == 3, 'vote_confidence: logits (B,C,N) expected')
+        b, c, n = logits.shape
+        table = None
+        if class_range is None:
+            c0, c1 = 0, c
+        elif isinstance(class_range, torch.Tensor):
+            _i32(class_range, 'class_range')
+            _shape(tuple(class_range.shape) == (b, 2), 'vote_confidence: class_range table (B,2) expected')
+            table, c0, c1 = class_range, 0, 0
+        else:
+            c0, c1 = int(class_range[0]), int(class_range[1])
+            _shape(0 <= c0 < c1 <= c, 'vote_confidence: class range must satisfy 0 <= c0 < c1 <= C')
+        conf = torch.empty((b, n), dtype=torch.float32, device=logits.device)
+        pred = torch.empty((b, n), dtype=torch.int32, device=logits.device)
+        with _Launch(logits) as s:
+            _lib.check(self.lib.pvcnn_vote_confidence(_p(logits), b, c, n, c0, c1, _p(table), _p(conf), _p(pred), s), 'vote_confidence')
+        return conf, pred
+
+    def vote_merge(self, conf, pred, shuffled, scene_conf, scene_pred, keys, mapping=None):
+        """update_scene_predictions in place on (scene_conf (P) float32, scene_pred (P) int64).  keys: the (P) int64 workspace, zero
+        before the first call (every call leaves it zero).  mapping: None, or contiguous (rows >= B, M) int64: vote (b, p) targets
+        mapping[b, shuffled[b, p]]."""
+        _f32(conf, 'conf'); _i32(pred, 'pred'); _f32(scene_conf, 'scene_conf')
+        for t, name in ((shuffled, 'shuffled'), (scene_pred, 'scene_pred'), (keys, 'keys')):
+            _dev(t, name)
+            _shape(t.dtype == torch.int64 and t.is_contiguous(), f'vote_merge: {name} must be a contiguous int64 tensor')
+        _shape(conf.dim() == 2 and conf.shape == pred.shape == shuffled.shape, 'vote_merge: conf, pred, shuffled (B,V) expected')
+        b, v = conf.shape
+        p = scene_conf.numel()
+        _shape(scene_pred.numel() == p and keys.numel() == p, 'vote_merge: scene_pred (P) and a (P) key workspace expected')
+        map_stride = 0
+        if mapping is not None:
+            _dev(mapping, 'mapping')
+            _shape(mapping.dtype == torch.int64 and mapping.is_contiguous() and mapping.dim() == 2 and mapping.shape[0] >= b,
+                   'vote_merge: mapping (>= B, M) contiguous int64 expected')
+            map_stride = mapping.shape[1]
+        with _Launch(conf) as s:
+            _lib.check(self.lib.pvcnn_vote_merge(_p(conf), _p(pred), _p(shuffled), _p(mapping), map_stride, b, v, p, _p(scene_conf),
+                                                 _p(scene_pred), _p(keys), keys.numel() * 8, s), 'vote_merge')
+
+    def seg_counts(self, gt, pred, num_classes, counts=None, wrap_negative=True):
+        """counts (3, C) int64 += [seen; positive; correct] of (gt, pred) (int64, P each); a new zeroed buffer when counts is None."""
+        for t, name in ((gt, 'gt'), (pred, 'pred')):
+            _dev(t, name)
+            _shape(t.dtype == torch.int64 and t.is_contiguous(), f'seg_counts: {name} must be a contiguous int64 tensor')
+        _shape(gt.numel() == pred.numel(), 'seg_counts: gt and pred must have the same number of points')
+        c = int(num_classes)
+        if counts is None:
+            counts = torch.zeros((3, c), dtype=torch.int64, device=gt.device)
+        _shape(counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == 3 * c, 'seg_counts: counts (3,C) int64')
+        with _Launch(gt) as s:
+            _lib.check(self.lib.pvcnn_seg_counts(_p(gt), _p(pred), gt.numel(), c, int(bool(wrap_negative)), _p(counts), s), 'seg_counts')
+        return counts
+
+    def seg_meter_update(self, logits, targets, counts=None, part_ranges=None, max_parts=0, rows=None, row_cursor=None):
+        """S3DIS mode (part_ranges None): counts (3C + 2) int64 += this batch.  ShapeNet mode: rows (capacity, max_parts + 1, 2) int32,
+        cloud b written at row *row_cursor + b (see include/pvcnn_hip.h)."""
+        _f32(logits, 'logits'); _dev(targets, 'targets')
+        _shape(logits.dim() == 3 and targets.dtype == torch.int64 and targets.is_contiguous()
+               and tuple(targets.shape) == (logits.shape[0], logits.shape[2]), 'seg_meter_update: logits (B,C,N), targets (B,N) int64')
+        b, c, n = logits.shape
+        with _Launch(logits) as s:
+            if part_ranges is None:
+                _shape(counts is not None and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == 3 * c + 2,
+                       'seg_meter_update: counts (3C+2) int64 expected')
+                rc = self.lib.pvcnn_seg_meter_update(_p(logits), _p(targets), b, c, n, None, 0, 0, _p(counts), None, None, 0, s)
+            else:
+                _i32(part_ranges, 'part_ranges')
+                _shape(part_ranges.dim() == 2 and part_ranges.shape[1] == 2, 'seg_meter_update: part_ranges (K,2) int32 expected')
+                _i32(rows, 'rows')
+                _shape(rows.dim() == 3 and rows.shape[1:] == (int(max_parts) + 1, 2), 'seg_meter_update: rows (capacity, max_parts+1, 2)')
+                if row_cursor is not None:
+                    _dev(row_cursor, 'row_cursor')
+                    _shape(row_cursor.dtype == torch.int64 and row_cursor.numel() == 1, 'seg_meter_update: row_cursor: one int64')
+                rc = self.lib.pvcnn_seg_meter_update(_p(logits), _p(targets), b, c, n, _p(part_ranges), part_ranges.shape[0], int(max_parts),
+                                                     None, _p(rows), _p(row_cursor), rows.shape[0], s)
+        _lib.check(rc, 'seg_meter_update')
+
+
 class _WeightBank:
     """Persistent f16x2 image pairs of registered weights (HipBackend.weight_bank_*).  An entry is keyed by (kind, data pointer,
     (Co, Ci)); `wanted` = the keys a forward pass asked for (take() misses note them), so a refresh computes what is used and nothing
