@@ -47,7 +47,7 @@ extern "C" {
 #define PVCNN_API
 #endif
 
-#define PVCNN_ABI_VERSION 13
+#define PVCNN_ABI_VERSION 14
 #define PVCNN_OK 0
 #define PVCNN_ERR_INVALID_ARGUMENT (-1)
 
@@ -611,6 +611,53 @@ PVCNN_API int pvcnn_seg_counts(const long long *gt, const long long *pred, long 
 PVCNN_API int pvcnn_seg_meter_update(const float *logits, const long long *targets, int B, int C, int N, const int *part_ranges,
                                      int num_part_classes, int max_parts, long long *counts, int *rows, const long long *row_cursor,
                                      long long row_capacity, void *stream);
+
+/* ---- (ABI v14) oriented-box overlaps of the Frustum-PVCNN KITTI metrics (csrc/boxes.hip): meters/kitti/frustum.py,
+ * meters/kitti/utils.get_box_iou_3d, evaluate/kitti/utils/iou.py (rotate_iou_gpu_eval), evaluate/kitti/utils/eval.py:58-103
+ * (d3_box_overlap), evaluate/kitti/frustum/eval.py:168-244 (update_predictions).  Every intersection is the same fp64 device function on
+ * fp32 corners (convex quads in bird's-eye view); no NaN comes out of finite corners: identical boxes give IoU 1, boxes that touch 0,
+ * a box of zero area intersects nothing, a union (or a criterion's denominator) of 0 gives 0.
+ *
+ * pvcnn_frustum_meter_update: MeterFrustumKitti.update in one launch, no host sync.
+ *   Box metrics (mask_logits NULL): predicted box = argmax (first maximum, NaN wins) over heading_scores (B, NH) and size_scores
+ *   (B, NS); heading = bin_centers[id] + heading_residuals[b, id], size = size_templates[id] + size_residuals[b, id] (fp32); the target
+ *   box from heading_bin_id_t / size_template_id_t (int64 (B)), heading_residual_t (B), size_residual_t (B, 3); corners as
+ *   get_box_corners_3d.  sums (2) fp64 += [sum iou_2d, sum iou_3d], reduced in a fixed order (bitwise reproducible);
+ *   counts (3 + 2 * num_classes) int64 += [B, -, #(iou_3d >= 0.7), #correct of class k (iou_3d >= thresholds[k]) ..., #seen of
+ *   class k ...], where box b is of class k when class_id_t[b] == class_ids[k] (int64 / fp64 tables of num_classes <= 64 entries).
+ *   A target id outside its table gives IoU 0.
+ *   Accuracy (mask_logits (B, C, N) fp32, mask_targets (B, N) int64): counts[0] += B * N, counts[1] += #(argmax over C == target). */
+PVCNN_API int pvcnn_frustum_meter_update(const float *center, const float *heading_scores, const float *heading_residuals,
+                                         const float *size_scores, const float *size_residuals, const float *center_t,
+                                         const long long *heading_bin_id_t, const float *heading_residual_t,
+                                         const long long *size_template_id_t, const float *size_residual_t, const long long *class_id_t,
+                                         int B, int NH, int NS, const float *bin_centers, const float *size_templates,
+                                         const long long *class_ids, const double *thresholds, int num_classes, const float *mask_logits,
+                                         const long long *mask_targets, int C, int N, double *sums, long long *counts, void *stream);
+/* pvcnn_box_iou_3d: get_box_iou_3d per pair of (B, 3, 8) fp32 corner sets -> iou_3d, iou_2d (B) fp64.  BEV on the upper face's x-z
+ * (corners 3, 2, 1, 0), height overlap from the y of corners 0 and 4, a box's volume = BEV area * |y0 - y4|. */
+PVCNN_API int pvcnn_box_iou_3d(const float *corners_1, const float *corners_t, int B, double *iou_3d, double *iou_2d, void *stream);
+/* pvcnn_rotate_iou: out (N, K) fp32 over rboxes (x, y, dx, dy, angle) fp32, boxes (N, 5) and query_boxes (K, 5), corners as
+ * rbbox_to_corners.  out[n, k] is the reference's dev_rotate_iou_eval(query_boxes[k], boxes[n], criterion): criterion -1: IoU,
+ * 0: inter / area(query box k), 1: inter / area(box n), other: the intersection area.  Areas are the corner quads' shoelace areas.
+ * N <= 65535 * 64; N == 0 or K == 0 launches nothing. */
+PVCNN_API int pvcnn_rotate_iou(const float *boxes, long long N, const float *query_boxes, long long K, int criterion, float *out,
+                               void *stream);
+/* pvcnn_box3d_overlap: d3_box_overlap fused.  bev_boxes (N, 5) / bev_query_boxes (K, 5) fp32 are the BEV columns of boxes (N, 7) /
+ * query_boxes (K, 7) fp64 (x, y, z, l, h, w, ry with the height axis z_axis dropped); rinc = the fp32 BEV intersection, then where
+ * rinc > 0 the height overlap iw of [c - d * z_center, c + d * (1 - z_center)] (c = column z_axis, d = column z_axis + 3) and
+ * inc = iw * rinc, volumes l * h * w, criterion as pvcnn_rotate_iou, in fp64; out (N, K) fp32, 0 where rinc <= 0 or iw <= 0. */
+PVCNN_API int pvcnn_box3d_overlap(const float *bev_boxes, const double *boxes, long long N, const float *bev_query_boxes,
+                                  const double *query_boxes, long long K, int criterion, int z_axis, double z_center, float *out,
+                                  void *stream);
+/* pvcnn_frustum_predictions: the decode of evaluate/kitti/frustum/eval.py:180-185 and update_predictions: row step + b of table
+ * (rows, 8) fp64 = [h, w, l, cx, cy, cz, angle, rgb_score] with cx = cos(r) x + sin(r) z, cy = y + h / 2, cz = cos(r) z - sin(r) x,
+ * angle = r + heading wrapped into [-pi, pi] (at most 64 steps of 2 pi each way), r = rotation_angle[b]; fp64 from the fp32 decode.
+ * Requires step + B <= rows. */
+PVCNN_API int pvcnn_frustum_predictions(const float *center, const float *heading_scores, const float *heading_residuals,
+                                        const float *size_scores, const float *size_residuals, int B, int NH, int NS,
+                                        const float *bin_centers, const float *size_templates, const double *rotation_angle,
+                                        const double *rgb_score, double *table, long long rows, long long step, void *stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must be imported before the dlopen, see above)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB_PATH = os.path.join(_CSRC, 'libpvcnn_hip.so')
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _vp, _i, _f, _sz, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
 _ll = ctypes.c_longlong
@@ -126,6 +126,11 @@ SIGNATURES = {
     'pvcnn_vote_merge': (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _ll, _vp, _vp, _vp, _sz, _vp]),
     'pvcnn_seg_counts': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp]),
     'pvcnn_seg_meter_update': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _ll, _vp]),
+    'pvcnn_frustum_meter_update': (_i, [_vp] * 11 + [_i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'pvcnn_box_iou_3d': (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    'pvcnn_rotate_iou': (_i, [_vp, _ll, _vp, _ll, _i, _vp, _vp]),
+    'pvcnn_box3d_overlap': (_i, [_vp, _vp, _ll, _vp, _vp, _ll, _i, _i, ctypes.c_double, _vp, _vp]),
+    'pvcnn_frustum_predictions': (_i, [_vp] * 5 + [_i, _i, _i] + [_vp] * 5 + [_ll, _ll, _vp]),
 }
 
 _lib = None

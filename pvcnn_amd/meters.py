@@ -1,4 +1,4 @@
-"""Segmentation meters of train.py on the device: drop-ins for the reference's meters/s3dis.py and meters/shapenet.py.
+"""Meters of train.py on the device: drop-ins for the reference's meters/s3dis.py, meters/shapenet.py and meters/kitti/frustum.py.
 
 Reference: `MeterS3DIS.update` makes 3 x num_classes `.item()` calls per batch and `MeterShapeNet.update` loops over clouds and classes
 with `.item()` -- host syncs that would dominate a replayed training step.  Here `update` only launches one kernel
@@ -7,14 +7,16 @@ into a hipGraph.  `compute` makes ONE device-to-host copy and does the final ari
 so its result is bit-equal to the reference meter's on the same tensors.
 
 Constructors, `reset` / `update(outputs, targets)` / `compute()` and `part_class_to_shape_part_classes` are the reference's, so these
-classes can stand in for `configs.train.meters[...]`.  Device buffers are allocated on the first `update` (on the outputs' device):
+classes can stand in for `configs.train.meters[...]`.  MeterFrustumKitti.update is one launch (csrc/boxes.hip:
+pvcnn_frustum_meter_update) where the reference decodes with torch, copies the corners to the host and clips them in Python.  Device buffers are allocated on the first `update` (on the outputs' device):
 run one eager update before capturing a graph, and give `MeterShapeNet.reserve` the number of clouds a captured loop will add.
 """
+import numpy as np
 import torch
 
 from .modules.functional import backend as _be
 
-__all__ = ['MeterS3DIS', 'MeterShapeNet', 'default_shape_name_to_part_classes']
+__all__ = ['MeterS3DIS', 'MeterShapeNet', 'MeterFrustumKitti', 'default_shape_name_to_part_classes']
 
 
 default_shape_name_to_part_classes = {
@@ -184,3 +186,90 @@ class MeterShapeNet:
 
     def compute(self):
         return shapenet_meter_value(self.rows())
+
+
+FRUSTUM_METRICS = ['iou_2d', 'iou_3d', 'accuracy', 'iou_3d_accuracy', 'iou_3d_class_accuracy']
+
+
+def frustum_class_thresholds(class_name_to_class_id):
+    """The per-class IoU threshold of the reference's update: 0.7 for 'Car', 0.5 for every other class (in the table's order)."""
+    return [0.7 if cls == 'Car' else 0.5 for cls in class_name_to_class_id.keys()]
+
+
+def frustum_meter_value(metric, class_names, sums, counts):
+    """The reference's MeterFrustumKitti.compute on sums [iou_2d, iou_3d] (floats) and counts [seen, correct, iou_3d correct,
+    correct per class K ..., seen per class K ...] (ints), classes in `class_names` order."""
+    k = len(class_names)
+    seen, correct, iou_3d_correct = counts[0], counts[1], counts[2]
+    if metric == 'iou_3d':
+        return sums[1] / seen
+    elif metric == 'iou_2d':
+        return sums[0] / seen
+    elif metric == 'accuracy':
+        return correct / seen
+    elif metric == 'iou_3d_accuracy':
+        return iou_3d_correct / seen
+    elif metric == 'iou_3d_class_accuracy':
+        return sum(counts[3 + i] / max(counts[3 + k + i], 1) for i in range(k)) / k
+    else:
+        raise KeyError
+
+
+class MeterFrustumKitti:
+    def __init__(self, num_heading_angle_bins, num_size_templates, size_templates, class_name_to_class_id,
+                 metric='iou_3d'):
+        super().__init__()
+        assert metric in FRUSTUM_METRICS
+        self.metric = metric
+        self.num_heading_angle_bins = num_heading_angle_bins
+        self.num_size_templates = num_size_templates
+        self.size_templates = size_templates.view(self.num_size_templates, 3)
+        # the reference's float32 arange (its values can differ from i * 2pi / NH by an ulp): uploaded, never recomputed
+        self.heading_angle_bin_centers = torch.arange(0, 2 * np.pi, 2 * np.pi / self.num_heading_angle_bins)
+        self.class_name_to_class_id = class_name_to_class_id
+        self.class_thresholds = frustum_class_thresholds(class_name_to_class_id)
+        # device state, allocated by the first eager update: sums (2) float64, counts (3 + 2K) int64 and the constant tables
+        self._sums = self._counts = self._tables = None
+        self.reset()
+
+    def reset(self):
+        if self._counts is not None:
+            self._sums.zero_()
+            self._counts.zero_()
+
+    def _alloc(self, device):
+        k = len(self.class_name_to_class_id)
+        self._sums = torch.zeros((2,), dtype=torch.float64, device=device)
+        self._counts = torch.zeros((3 + 2 * k,), dtype=torch.int64, device=device)
+        self._tables = (self.heading_angle_bin_centers.to(device=device, dtype=torch.float32).contiguous(),
+                        self.size_templates.to(device=device, dtype=torch.float32).contiguous(),
+                        torch.tensor(list(self.class_name_to_class_id.values()), dtype=torch.int64, device=device),
+                        torch.tensor(self.class_thresholds, dtype=torch.float64, device=device))
+
+    def update(self, outputs, targets):
+        ref = outputs['mask_logits'] if self.metric == 'accuracy' else outputs['center']
+        if self._counts is None or self._counts.device != ref.device:
+            self._alloc(ref.device)
+        if self.metric == 'accuracy':
+            _be._backend.frustum_meter_accuracy(_float_logits(outputs['mask_logits']), _long_targets(targets['mask_logits']),
+                                                self._counts)
+            return
+        heads = tuple(_float_logits(outputs[k]) for k in
+                      ('center', 'heading_scores', 'heading_residuals', 'size_scores', 'size_residuals'))
+        tgt = (_float_logits(targets['center']), _long_targets(targets['heading_bin_id']),
+               _float_logits(targets['heading_residual']), _long_targets(targets['size_template_id']),
+               _float_logits(targets['size_residual']), _long_targets(targets['class_id']))
+        bin_centers, templates, class_ids, thresholds = self._tables
+        _be._backend.frustum_meter_update(heads, tgt, bin_centers, templates, class_ids, thresholds, self._sums, self._counts)
+
+    def state(self):
+        """(sums [iou_2d, iou_3d] as floats, counts as ints): one device-to-host copy."""
+        k = len(self.class_name_to_class_id)
+        if self._counts is None:
+            return [0.0, 0.0], [0] * (3 + 2 * k)
+        packed = torch.cat([self._sums.view(torch.int64), self._counts]).cpu()
+        return packed[:2].view(torch.float64).tolist(), packed[2:].tolist()
+
+    def compute(self):
+        sums, counts = self.state()
+        return frustum_meter_value(self.metric, list(self.class_name_to_class_id.keys()), sums, counts)

@@ -1396,6 +1396,109 @@ class HipBackend:
                                                      None, _p(rows), _p(row_cursor), rows.shape[0], s)
         _lib.check(rc, 'seg_meter_update')
 
+    # ---- oriented boxes (csrc/boxes.hip, ABI v14): meters/kitti and the KITTI AP overlaps on the device ------------------------------
+    @staticmethod
+    def _box_heads(center, heading_scores, heading_residuals, size_scores, size_residuals):
+        for t, name in ((center, 'center'), (heading_scores, 'heading_scores'), (heading_residuals, 'heading_residuals'),
+                        (size_scores, 'size_scores'), (size_residuals, 'size_residuals')):
+            _f32(t, name)
+        b, nh = heading_scores.shape
+        ns = size_scores.shape[1]
+        _shape(tuple(center.shape) == (b, 3) and tuple(heading_residuals.shape) == (b, nh) and tuple(size_scores.shape) == (b, ns)
+               and tuple(size_residuals.shape) == (b, ns, 3), 'box heads: center (B,3), heading (B,NH) x2, size (B,NS), (B,NS,3)')
+        return b, nh, ns
+
+    @staticmethod
+    def _box_tables(bin_centers, size_templates, nh, ns):
+        _f32(bin_centers, 'heading_angle_bin_centers'); _f32(size_templates, 'size_templates')
+        _shape(bin_centers.numel() == nh and size_templates.numel() == 3 * ns,
+               'box tables: NH heading bin centers and (NS, 3) size templates expected')
+
+    def frustum_meter_update(self, outputs, targets, bin_centers, size_templates, class_ids, thresholds, sums, counts):
+        """MeterFrustumKitti.update of the box metrics: sums (2) float64 += [iou_2d, iou_3d], counts (3 + 2K) int64 += [boxes, -,
+        iou_3d >= 0.7, correct K | seen K].  outputs / targets: (center, heading_scores, heading_residuals, size_scores, size_residuals)
+        float32 and (center, heading_bin_id int64, heading_residual, size_template_id int64, size_residual, class_id int64)."""
+        b, nh, ns = self._box_heads(*outputs)
+        self._box_tables(bin_centers, size_templates, nh, ns)
+        center_t, hid_t, hres_t, sid_t, sres_t, cls_t = targets
+        for t, name in ((center_t, 'center'), (hres_t, 'heading_residual'), (sres_t, 'size_residual')):
+            _f32(t, name)
+        for t, name in ((hid_t, 'heading_bin_id'), (sid_t, 'size_template_id'), (cls_t, 'class_id'), (class_ids, 'class_ids'),
+                        (counts, 'counts')):
+            _dev(t, name)
+            _shape(t.dtype == torch.int64 and t.is_contiguous(), f'frustum_meter_update: {name} must be a contiguous int64 tensor')
+        _dev(thresholds, 'thresholds'); _dev(sums, 'sums')
+        k = class_ids.numel()
+        _shape(tuple(center_t.shape) == (b, 3) and hid_t.numel() == b and hres_t.numel() == b and sid_t.numel() == b
+               and tuple(sres_t.shape) == (b, 3) and cls_t.numel() == b, 'frustum_meter_update: targets of B boxes expected')
+        _shape(thresholds.dtype == torch.float64 and thresholds.numel() == k and sums.dtype == torch.float64 and sums.numel() == 2
+               and counts.numel() == 3 + 2 * k, 'frustum_meter_update: thresholds (K) / sums (2) float64, counts (3 + 2K) int64')
+        with _Launch(outputs[0]) as s:
+            _lib.check(self.lib.pvcnn_frustum_meter_update(*(_p(t) for t in outputs), *(_p(t) for t in targets), b, nh, ns,
+                                                           _p(bin_centers), _p(size_templates), _p(class_ids), _p(thresholds), k,
+                                                           None, None, 0, 0, _p(sums), _p(counts), s), 'frustum_meter_update')
+
+    def frustum_meter_accuracy(self, mask_logits, mask_targets, counts):
+        """MeterFrustumKitti.update, metric 'accuracy': counts[0] += B*N, counts[1] += #(argmax(mask_logits, 1) == target)."""
+        _f32(mask_logits, 'mask_logits'); _dev(mask_targets, 'mask_targets'); _dev(counts, 'counts')
+        _shape(mask_logits.dim() == 3 and mask_targets.dtype == torch.int64 and mask_targets.is_contiguous()
+               and tuple(mask_targets.shape) == (mask_logits.shape[0], mask_logits.shape[2]),
+               'frustum_meter_accuracy: mask_logits (B,C,N) float32, targets (B,N) int64')
+        _shape(counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() >= 2, 'frustum_meter_accuracy: counts int64')
+        b, c, n = mask_logits.shape
+        with _Launch(mask_logits) as s:
+            _lib.check(self.lib.pvcnn_frustum_meter_update(*([None] * 11), b, 0, 0, None, None, None, None, 0, _p(mask_logits),
+                                                           _p(mask_targets), c, n, None, _p(counts), s), 'frustum_meter_accuracy')
+
+    def box_iou_3d(self, corners_1, corners_t):
+        """(B, 3, 8) float32 corner sets -> (iou_3d, iou_2d), (B) float64 each (get_box_iou_3d per pair)."""
+        _f32(corners_1, 'corners_1'); _f32(corners_t, 'corners_t')
+        _shape(corners_1.dim() == 3 and tuple(corners_1.shape[1:]) == (3, 8) and corners_1.shape == corners_t.shape,
+               'box_iou_3d: two (B,3,8) corner tensors expected')
+        b = corners_1.shape[0]
+        iou_3d = torch.empty((b,), dtype=torch.float64, device=corners_1.device)
+        iou_2d = torch.empty_like(iou_3d)
+        with _Launch(corners_1) as s:
+            _lib.check(self.lib.pvcnn_box_iou_3d(_p(corners_1), _p(corners_t), b, _p(iou_3d), _p(iou_2d), s), 'box_iou_3d')
+        return iou_3d, iou_2d
+
+    def rotate_iou(self, boxes, query_boxes, criterion=-1, boxes_3d=None, query_boxes_3d=None, z_axis=1, z_center=1.0):
+        """(N, K) float32 overlaps of rboxes (N, 5) and (K, 5) float32 (x, y, dx, dy, angle).  With boxes_3d / query_boxes_3d
+        ((N, 7) / (K, 7) float64, whose BEV columns the rboxes are): d3_box_overlap instead of the BEV overlap."""
+        _f32(boxes, 'boxes'); _f32(query_boxes, 'query_boxes')
+        _shape(boxes.dim() == 2 and boxes.shape[1] == 5 and query_boxes.dim() == 2 and query_boxes.shape[1] == 5,
+               'rotate_iou: boxes (N,5) and query_boxes (K,5) expected')
+        n, k = boxes.shape[0], query_boxes.shape[0]
+        out = torch.zeros((n, k), dtype=torch.float32, device=boxes.device)
+        with _Launch(boxes) as s:
+            if boxes_3d is None:
+                rc = self.lib.pvcnn_rotate_iou(_p(boxes), n, _p(query_boxes), k, int(criterion), _p(out), s)
+            else:
+                for t, name, rows in ((boxes_3d, 'boxes_3d', n), (query_boxes_3d, 'query_boxes_3d', k)):
+                    _dev(t, name)
+                    _shape(t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, 7),
+                           f'box3d_overlap: {name} ({rows},7) contiguous float64 expected')
+                rc = self.lib.pvcnn_box3d_overlap(_p(boxes), _p(boxes_3d), n, _p(query_boxes), _p(query_boxes_3d), k, int(criterion),
+                                                  int(z_axis), float(z_center), _p(out), s)
+        _lib.check(rc, 'rotate_iou' if boxes_3d is None else 'box3d_overlap')
+        return out
+
+    def frustum_predictions(self, heads, bin_centers, size_templates, rotation_angle, rgb_score, table, step):
+        """Rows step .. step+B-1 of table (rows, 8) float64 = update_predictions of the decoded boxes.  heads: (center,
+        heading_scores, heading_residuals, size_scores, size_residuals) float32; rotation_angle, rgb_score (B) float64."""
+        b, nh, ns = self._box_heads(*heads)
+        self._box_tables(bin_centers, size_templates, nh, ns)
+        for t, name in ((rotation_angle, 'rotation_angle'), (rgb_score, 'rgb_score'), (table, 'predictions')):
+            _dev(t, name)
+            _shape(t.dtype == torch.float64 and t.is_contiguous(), f'frustum_predictions: {name} must be a contiguous float64 tensor')
+        _shape(rotation_angle.numel() == b and rgb_score.numel() == b and table.dim() == 2 and table.shape[1] == 8,
+               'frustum_predictions: rotation_angle, rgb_score (B), table (rows, 8) expected')
+        _shape(0 <= int(step) and int(step) + b <= table.shape[0], 'frustum_predictions: the batch does not fit in the table')
+        with _Launch(heads[0]) as s:
+            _lib.check(self.lib.pvcnn_frustum_predictions(*(_p(t) for t in heads), b, nh, ns, _p(bin_centers), _p(size_templates),
+                                                          _p(rotation_angle), _p(rgb_score), _p(table), table.shape[0], int(step), s),
+                       'frustum_predictions')
+
 
 class _WeightBank:
     """Persistent f16x2 image pairs of registered weights (HipBackend.weight_bank_*).  An entry is keyed by (kind, data pointer,
