@@ -15,7 +15,11 @@ reducer's autograd hooks launch them, overlapped with the rest of backward -- or
 captured and the all-reduces + Adam issued after each replay; `config.step_issue` says which).  `value` / `ms_per_step` are that region; `eager_value` is the same step issued launch by launch from
 Python (timed separately, after the timed region).  `--eager` times the eager step instead.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: metric, value, unit, ms_per_step, dtype,
+config and the other fields that cost nothing beyond the timed region.  Everything else runs only under `--full`, after the timed
+region and the dump: `eager_value`, the objects below, the variants and, with N GPUs, `config.allreduce_alone_us_per_step`.
+
+Extra objects on the JSON line (--full):
   roofline     : the hot path's headline kernel (trilinear_devoxelize fwd at the R=32 stage,
                  16x64x4096 points from a 16x64x32^3 grid), timed twice: LIVE in this process with HIP events on the
                  launch stream around every launch of it in instrumented eager steps AFTER the timed region (a replayed
@@ -318,7 +322,7 @@ def run_variant(config, extra_args=(), env=None, steps=20, warmup=5, timeout=300
     process would share the weight bank and the allocator pools with the first): -> its JSON line, or {'error': ...}."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), '--config', config, '--steps', str(steps), '--warmup', str(warmup),
-           '--no-cpu-baseline', '--no-variants', *extra_args]
+           '--full', '--no-cpu-baseline', '--no-variants', *extra_args]
     try:
         out = subprocess.run(cmd, env={**os.environ, **(env or {})}, capture_output=True, text=True, timeout=timeout)
         lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -471,7 +475,10 @@ def main():
     ap.add_argument('--config', default='cfg2', choices=['cfg2', 'cfg3', 'cfg4', 'cfg5'],
                     help='BASELINE.json configs: cfg2 PVCNN S3DIS (the headline, default); cfg3 PVCNN++ S3DIS B=8 N=8192; cfg4 PVCNN ShapeNet '
                          'B=8/GPU N=2048; cfg5 Frustum-PVCNN KITTI B=4/GPU... (per-GPU batches of the 8-GPU runs unless --batch is given)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also measure what the headline figure does not need: eager_value, the per-kernel HIP '
+                         'events and rooflines, the variants, the CPU baseline and (N > 1) the collectives alone')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: leave out cpu_baseline')
     ap.add_argument('--cpu-sample-batch', type=int, default=0, help='clouds per CPU-baseline step (0 = the same batch as the GPU run)')
     ap.add_argument('--bucket-mb', type=float, default=8.0)
     ap.add_argument('--eager', action='store_true',
@@ -489,7 +496,7 @@ def main():
                          '.max / .repeat / torch.cat, nn.Sequential heads with nn.Dropout and nn.Conv1d as modules) on pvcnn_amd.modules -- '
                          'what a user gets who swaps the `modules` package and nothing else -- instead of pvcnn_amd.workload\'s composition')
     ap.add_argument('--no-variants', action='store_true',
-                    help='do not add reference_composition_value / fp32_mfma_value to the line (each is this command again in a process of its own, 20 steps)')
+                    help='--full: do not add reference_composition_value / fp32_mfma_value to the line (each is this command again in a process of its own, 20 steps)')
     ap.add_argument('--dry-collectives', action='store_true',
                     help='no GPU needed: run the N-rank step SEQUENCING (both orderings of pvcnn_amd/graph.py\'s multi-rank branch, issued eagerly) '
                          'on a reduced-width network over gloo / CPU tensors with the CPU oracle as native backend and check it against the '
@@ -603,6 +610,8 @@ def main():
         from pvcnn_amd.optim import FlatAdam
         opt = FlatAdam(reducer, lr=1e-3, weight_decay=1e-5)
 
+    # installed in every run, enabled only by --full after the timed region: the step is captured (or, --eager, issued) through the
+    # same calls with and without --full
     clock = KernelClock(seam._backend)
     clock.install()
 
@@ -664,9 +673,11 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, model, loss)     # before the eager steps below move the parameters on
 
+    # ---- --full only from here on: what the headline figure does not need, measured after the timed region and the dump ----
+
     # ---- the step's collectives alone (all buckets, back to back, nothing to overlap with): what NOT overlapping them would cost ----
     comm_us = None
-    if multi:
+    if multi and args.full:
         for _ in range(3):
             for b in reducer.buckets:
                 dist.all_reduce(b.flat)
@@ -681,7 +692,7 @@ def main():
     # ---- the same step issued launch by launch (host-bound on one Python thread): eager_value ----
     eager_steps = min(args.steps, 20)
     eager_elapsed = None
-    if graphed is not None:
+    if graphed is not None and args.full:
         # (the eager steps allocate from the default stream's pool, which is empty after a capture: the caching allocator needs a few
         # steps of its own before a step stops calling hipMalloc -- with 3 warm-up steps this figure read 1 100 ... 2 150 clouds/s from
         # process to process on the same code)
@@ -699,13 +710,16 @@ def main():
             eager_elapsed = t.item()
 
     # ---- per-kernel HIP events: instrumented eager steps (every watched launch carries an event pair on the launch stream) ----
-    event_overhead_us = KernelClock.event_pair_overhead_us()
-    clock.enabled = True
-    for _ in range(eager_steps):
-        eager_step()
-    fence()
-    clock.enabled = False
-    kernels = clock.summary(event_overhead_us)
+    # (without --full: no kernels, hence no roofline / roofline_mfma below)
+    kernels = []
+    if args.full:
+        event_overhead_us = KernelClock.event_pair_overhead_us()
+        clock.enabled = True
+        for _ in range(eager_steps):
+            eager_step()
+        fence()
+        clock.enabled = False
+        kernels = clock.summary(event_overhead_us)
     clock.uninstall()
 
     if rank == 0:
@@ -798,31 +812,34 @@ def main():
                        'rccl_ranks': world if multi else 0, 'per_rank_ms_per_step': per_rank_ms,
                        'gradient_buckets': len(reducer.buckets), 'allreduce_alone_us_per_step': comm_us},
             'timed_region': timed,
-            'eager_value': None if eager_elapsed is None else round(global_batch * eager_steps / eager_elapsed, 2),
-            'eager_ms_per_step': None if eager_elapsed is None else round(eager_elapsed / eager_steps * 1e3, 3),
-            'roofline': roofline,
-            # the step's largest MFMA-bound launch (Conv3d forward of the R=32 stage), same event timing
-            'roofline_mfma': None if mfma is None else {
-                'bound': 'mfma', 'kernel': mfma['kernel'] + ' (Conv3d 3x3x3 forward / backward-data of the largest stage)',
-                'in_graph_us': mfma_graph_us, 'live_frac': mfma['frac_of_peak'],
-                'shape_BCiCoR': mfma['shape_BCiCoR'], 'achieved': round(mfma['executed_mfma_TFLOPs'] * mfma_price, 1), 'peak': mfma['peak_TFLOPs'],
-                'unit': 'TFLOP/s', 'frac': round(mfma['frac_of_peak'] * mfma_price, 4), 'avg_us': mfma['avg_us'], 'algorithmic_GFLOP': mfma['GFLOP'],
-                'effective_fp32_TFLOPs': mfma['effective_TFLOPs'], 'x_fp32_mfma_peak_157TF': mfma['x_fp32_mfma_peak'],
-                'note': 'achieved = MFMA flops actually executed (f16x2: 3 fp16 partial products per fp32 product; bf16x3: 6) / launch time; '
-                        'effective = algorithmic 2*B*R^3*27*Ci*Co / launch time; frac is priced on the slower of live events and the '
-                        'committed in-graph rocprofv3 average (in_graph_us).  frac = pipe busy x clock / 2.4 GHz: the counters of the '
-                        'matrix kernels inside this step are profiles/r06_pmc_mfma_bench_table.md (busy share of the cycles, effective '
-                        'clock), the same binaries on random and on constant operands profiles/r06_pmc_mfma_fill_probe.jsonl, and what '
-                        'the parts of this kernel cost next to its bare MFMA stream profiles/r06_ablate_conv_fwd.jsonl (DESIGN 4)'},
-            'kernels': kernels,
-            'kernels_note': 'per-launch HIP event pairs inside the eager steps behind the timed region (median per launch shape, minus the '
-                            'empty-pair time): host-paced, i.e. an upper bound per kernel; the in-graph durations are profiles/kernel_durations*.json',
         }
+        if args.full:
+            line.update({
+                'eager_value': None if eager_elapsed is None else round(global_batch * eager_steps / eager_elapsed, 2),
+                'eager_ms_per_step': None if eager_elapsed is None else round(eager_elapsed / eager_steps * 1e3, 3),
+                'roofline': roofline,
+                # the step's largest MFMA-bound launch (Conv3d forward of the R=32 stage), same event timing
+                'roofline_mfma': None if mfma is None else {
+                    'bound': 'mfma', 'kernel': mfma['kernel'] + ' (Conv3d 3x3x3 forward / backward-data of the largest stage)',
+                    'in_graph_us': mfma_graph_us, 'live_frac': mfma['frac_of_peak'],
+                    'shape_BCiCoR': mfma['shape_BCiCoR'], 'achieved': round(mfma['executed_mfma_TFLOPs'] * mfma_price, 1), 'peak': mfma['peak_TFLOPs'],
+                    'unit': 'TFLOP/s', 'frac': round(mfma['frac_of_peak'] * mfma_price, 4), 'avg_us': mfma['avg_us'], 'algorithmic_GFLOP': mfma['GFLOP'],
+                    'effective_fp32_TFLOPs': mfma['effective_TFLOPs'], 'x_fp32_mfma_peak_157TF': mfma['x_fp32_mfma_peak'],
+                    'note': 'achieved = MFMA flops actually executed (f16x2: 3 fp16 partial products per fp32 product; bf16x3: 6) / launch time; '
+                            'effective = algorithmic 2*B*R^3*27*Ci*Co / launch time; frac is priced on the slower of live events and the '
+                            'committed in-graph rocprofv3 average (in_graph_us).  frac = pipe busy x clock / 2.4 GHz: the counters of the '
+                            'matrix kernels inside this step are profiles/r06_pmc_mfma_bench_table.md (busy share of the cycles, effective '
+                            'clock), the same binaries on random and on constant operands profiles/r06_pmc_mfma_fill_probe.jsonl, and what '
+                            'the parts of this kernel cost next to its bare MFMA stream profiles/r06_ablate_conv_fwd.jsonl (DESIGN 4)'},
+                'kernels': kernels,
+                'kernels_note': 'per-launch HIP event pairs inside the eager steps behind the timed region (median per launch shape, minus the '
+                                'empty-pair time): host-paced, i.e. an upper bound per kernel; the in-graph durations are profiles/kernel_durations*.json',
+            })
         if graph_error:
             line['graph_error'] = graph_error
         if graphed is not None and graphed.capture_error:
             line['collective_capture_error'] = graphed.capture_error
-        if world == 1 and not args.no_variants and not args.reference_composition and not args.eager and args.config in ('cfg2', 'cfg3', 'cfg4'):
+        if args.full and world == 1 and not args.no_variants and not args.reference_composition and not args.eager and args.config in ('cfg2', 'cfg3', 'cfg4'):
             # the same command twice more, each in a process of its own (20 timed steps): what a user of the reference gets who swaps
             # the `modules` package and keeps their models/ unchanged, and (cfg2) the single-rounding fp32-MFMA arithmetic
             passthrough = ['--batch', str(args.batch), '--points', str(args.points), '--width', str(args.width)]
@@ -840,7 +857,7 @@ def main():
                                       'what': 'this command under PVCNN_CONV_MATH=fp32 PVCNN_PW_MATH=fp32: every Conv3d / 1x1 product on '
                                               'v_mfma_f32_32x32x2_f32 (single-rounding fp32 MFMA) instead of the f16x2 split'}
                                      if 'error' not in v else v)
-        if world == 1 and not args.no_cpu_baseline and args.config == 'cfg2':
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config == 'cfg2':
             line['cpu_baseline'] = cpu_baseline(args, args.cpu_sample_batch or args.batch)
     # the JSON line must be the LAST line of the job's stdout: RCCL writes a start-up banner ("RCCL version : ...", five lines per rank)
     # through C stdio, which -- into a pipe -- stays in libc's buffer until the process exits, i.e. behind anything Python has printed.

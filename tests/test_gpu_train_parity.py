@@ -213,7 +213,11 @@ def test_pvconv_train_gradients_match_the_oracle_stack(hip, oracle, cin, cout, r
         return (out[0] * tgt).mean() + out[0].square().mean()
 
     label = f'PVConv({cin}->{cout}, R={r}, N={n}, se={se}, normalize={normalize})'
-    res = _run_three(lambda: PVConv(cin, cout, 3, r, with_se=se, normalize=normalize), make, loss_fn, oracle)
+    # the fp32 checker's Conv3d on ATen's own CPU kernels, not oneDNN's: oneDNN's weight gradient sums in an order chosen by the host's
+    # ISA, and on AVX-512 hosts the 64 -> 64 layer at R = 32 lands 5.9e-4 (per tensor) from the fp64 truth through the train-mode
+    # BatchNorm behind it -- the checker, not the HIP path (1.5e-6), would decide this test; ATen's kernels keep it within ~1e-6 of the truth
+    with torch.backends.mkldnn.flags(enabled=False):
+        res = _run_three(lambda: PVConv(cin, cout, 3, r, with_se=se, normalize=normalize), make, loss_fn, oracle)
     rows = _report(label, *res)
     assert abs(res[0][0] - res[1][0]) <= TOL_LOSS * max(abs(res[1][0]), 1.0)
     bad = [(k, a) for k, a, _, _ in rows if a > TOL_LAYER]

@@ -730,6 +730,31 @@ def test_the_roofline_launch_is_priced_on_the_slower_trustworthy_timing():
     assert bench.price_launch_us(31.1, 35.3, 0.0)[0] == 35.3         # (in_graph_us() reports a stale trace as None / nothing)
 
 
+def test_bench_full_is_an_option_and_the_variants_run_with_it(monkeypatch):
+    """A plain bench.py run measures the headline only; `--full` adds the rest.  The variants copy eager_value from their own line,
+    so their processes run with --full (and without variants or CPU baseline of their own)."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and '--full' in out.stdout
+    spec = importlib.util.spec_from_file_location('bench_for_variants', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    seen = []
+
+    def fake_run(cmd, **kw):
+        seen.append(cmd)
+        return subprocess.CompletedProcess(cmd, 0, stdout=json.dumps({'metric': 'm', 'value': 1.0, 'eager_value': 0.5}) + '\n', stderr='')
+    monkeypatch.setattr(subprocess, 'run', fake_run)
+    v = bench.run_variant('cfg2', ['--reference-composition'])
+    assert v['eager_value'] == 0.5
+    assert {'--full', '--no-variants', '--no-cpu-baseline', '--reference-composition'} <= set(seen[0])
+
+
 def test_trace_overlap_reports_what_ran_next_to_a_kernel(tmp_path):
     """tools/trace_overlap.py (the evidence of profiles/ab/r05i): per launch of the named kernel its duration, whether anything else
     was on the chip, and the time each other kernel shared with it."""

@@ -3,7 +3,7 @@
 # Outputs -> gpurun_out/$ROUND/; copy what is judged to profiles/ as ${ROUND}_*  (tools/publish_evidence.sh does that).
 R=${GRAFT_REPO_ROOT:-$PWD}; RD=${ROUND:-r05}; O=$R/gpurun_out/$RD; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py"
+BENCH="python $R/bench.py --full"
 # 1. rocprofv3 kernel trace + stats of the bench command -> kernel stats, steady-state reduction of the 100 replayed steps, and the
 #    per-launch in-graph durations bench.py prices its rooflines on (profiles/kernel_durations.json): FIRST, so that the bench lines
 #    of step 2 already carry this round's in-graph figures
@@ -67,14 +67,14 @@ done
  python tools/pwbench.py 2>/dev/null | grep "^{" > $O/pwbench.jsonl
  python tools/fpsbench.py 2>/dev/null | grep "^{" > $O/fpsbench.jsonl
  python tools/sparse_probe.py 2>/dev/null | grep "B=" > $O/sparse_probe.txt
- PVCNN_CONV_MATH=fp32 PVCNN_PW_MATH=fp32 timeout 300 python bench.py --no-cpu-baseline --no-variants --steps 40 --warmup 10 2>/dev/null | tail -1 > $O/bench_fp32_mfma.json
+ PVCNN_CONV_MATH=fp32 PVCNN_PW_MATH=fp32 timeout 300 python bench.py --full --no-cpu-baseline --no-variants --steps 40 --warmup 10 2>/dev/null | tail -1 > $O/bench_fp32_mfma.json
  timeout 120 python tools/step_profile.py --rows 70 > $O/step_profile.txt 2>/dev/null)
 fi
 for c in cfg3 cfg4 cfg5; do
   rm -rf /tmp/kt_$c; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$c -- $BENCH --config $c --no-cpu-baseline --no-variants --steps 40 --warmup 10 > $O/${c}_under_rocprof.log 2>&1
   t=$(find /tmp/kt_$c -name "*kernel_trace.csv" | head -1); python $R/tools/trace_steady.py $t 40 50 50 --json $O/kernel_durations_$c.json > $O/${c}_steady_state.txt 2>&1
   cp $O/kernel_durations_$c.json $R/profiles/kernel_durations_$c.json
-  (cd $R && timeout 300 python bench.py --config $c --no-cpu-baseline --steps 40 --warmup 10 2>/dev/null | tail -1 > $O/bench_$c.json)
+  (cd $R && timeout 300 python bench.py --full --config $c --no-cpu-baseline --steps 40 --warmup 10 2>/dev/null | tail -1 > $O/bench_$c.json)
 done
 rm -f $O/*_under_rocprof.log
 ls -la $O

@@ -19,7 +19,7 @@ python $R/bench.py --gpus 4 --dry-collectives 2>/dev/null | tail -1 > $O/dry_col
 : > $O/summary.txt
 for N in $Ns; do
   if [ "$N" -gt "$have" ]; then echo "N=$N skipped: $have GPU(s) present" | tee -a $O/summary.txt; continue; fi
-  (cd $R && timeout 900 python bench.py --gpus $N --steps 20 --warmup 5 --no-cpu-baseline --no-variants 2>$O/N$N.err | tail -1 > $O/N$N.json)
+  (cd $R && timeout 900 python bench.py --gpus $N --steps 20 --warmup 5 --full --no-cpu-baseline --no-variants 2>$O/N$N.err | tail -1 > $O/N$N.json)
   python - $N $O/N$N.json <<'PY' | tee -a $O/summary.txt || rc=1
 import json, sys
 n, path = int(sys.argv[1]), sys.argv[2]

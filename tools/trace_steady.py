@@ -6,7 +6,7 @@ usage: trace_steady.py <kernel_trace.csv> <timed_steps> [top] [skip_last] [--by-
  launch of a step, i.e. per layer: launches of one template with equal grids (Conv3d 9->64 and 64->64 at 32^3) are told apart by order)
 (--json: machine-readable per-launch-of-a-step averages of every pvcnn:: kernel -- profiles/kernel_durations.json, read by bench.py)
 Training steps are delimited by the optimizer phase (runs of fused Adam's multi_tensor_apply kernels, or of pvcnn_amd.optim.FlatAdam's kernels);
-the `timed_steps` complete steps before the last `skip_last` ones are aggregated, i.e. bench.py's timed region (bench.py runs
+the `timed_steps` complete steps before the last `skip_last` ones are aggregated, i.e. bench.py's timed region (bench.py --full runs
 min(steps, 20) fully instrumented steps AFTER it: skip_last = 20 for the default 100 steps)."""
 import csv
 import sys
