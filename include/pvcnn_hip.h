@@ -47,7 +47,7 @@ extern "C" {
 #define PVCNN_API
 #endif
 
-#define PVCNN_ABI_VERSION 14
+#define PVCNN_ABI_VERSION 15
 #define PVCNN_OK 0
 #define PVCNN_ERR_INVALID_ARGUMENT (-1)
 
@@ -193,6 +193,54 @@ PVCNN_API int pvcnn_fps(const float *coords, int B, int N, int M, float *distanc
  */
 PVCNN_API int pvcnn_mask_select(const uint8_t *mask, int B, int N, int M, const int32_t *choices, const int64_t *seed,
                       int32_t *selected, int32_t *count, void *stream);
+
+/* ---- batches assembled on the device (ABI v15; pvcnn_amd/data.py) --------------------------------------------------
+ * replace one iteration of the reference's DataLoader (datasets/s3dis.py:81-94, shapenet.py:62-81, kitti/frustum.py:95-147 +
+ * default_collate) for a split held in device memory.  One launch, never allocates, every pointer is device memory.
+ * The store: `rows` (R, C) fp32, ROW-major and packed (item i owns rows offsets[i] .. offsets[i+1]; C = 9 / 6 / 4), `labels` (R) of
+ * label_bytes each (1: uint8, 2: int16, 4: int32, 8: int64), `offsets` (W + 1) int64.  Row addressing is 64-bit.
+ * Sample b of the batch is item order[cursor[0] + b] (`order` (order_len) int64, `cursor` one int64 word or NULL = 0), read on the
+ * device: a captured launch walks an epoch when the caller adds B to the cursor after it.  Positions, items and parity choices out of
+ * range are clamped (no out-of-bounds access); an empty item yields zeros.
+ * Randomness as pvcnn_mask_select: `choices` (B, N) int32 rows within the item (PARITY MODE, with the other draws of the dataset
+ * kind; bit-identical to the reference for numpy's draws), or, when choices is NULL, a Philox4x32-10 stream keyed by `seed` (two
+ * int64 words in device memory: key, stream id).
+ * Outputs are what default_collate makes of the reference's items: features (B, C_out, N) fp32, targets (B, N) int64, ...
+ */
+/* LDS the S3DIS launch takes in device mode for N samples from items of at most max_n rows (0: no selection without replacement). */
+PVCNN_API size_t pvcnn_batch_lds_bytes(int N, int max_n);
+/* S3DIS: C = 9; C_out = 9, or 6 (without the normalised coordinates).  np.random.choice(n, N, replace = n < N): in device mode items
+ * with n >= N are sampled WITHOUT replacement by a sort in LDS; max_n = the largest item of the store, refused beyond 8192 when it is
+ * >= N. */
+PVCNN_API int pvcnn_batch_s3dis(const float *rows, const void *labels, int label_bytes, const int64_t *offsets, long long W, int max_n,
+                      const int64_t *order, long long order_len, const int64_t *cursor, int B, int N, int C_out,
+                      const int32_t *choices, const int64_t *seed, float *features, int64_t *targets, void *stream);
+/* ShapeNet: C = 6 (normalised coords, normals); features (B, 3 [+ 3 if with_normal] [+ num_shapes], N) with the one-hot plane of
+ * shape_ids[item] (num_shapes = 0: none).  jitter_on: coord += fp32(clip(0.01 z, -0.05, 0.05)), z from `jitter` (B, 3, N) fp64 in
+ * parity mode, Box-Muller fp32 in device mode. */
+PVCNN_API int pvcnn_batch_shapenet(const float *rows, const void *labels, int label_bytes, const int64_t *offsets, long long W,
+                         const int32_t *shape_ids, const int64_t *order, long long order_len, const int64_t *cursor, int B, int N,
+                         int with_normal, int num_shapes, int jitter_on, const int32_t *choices, const double *jitter,
+                         const int64_t *seed, float *features, int64_t *targets, void *stream);
+/* Frustum-KITTI with ground truth: C = 4 (rows already rotated when frustum_rotate), labels = the mask.  Per item, computed on the
+ * host: item_f64 (W, 4) centre x y z and dist; item_f32 (W, K + 5) one-hot (K classes), heading residual without / with flip, size
+ * residual; item_i64 (W, 4) heading bin without / with flip, size template id, class id.  random_flip: x and centre x negated, the
+ * flipped heading taken, when flip[b] > 0.5 (`flip` (B) fp64 in parity mode); random_shift: clip(z dist 0.05, 0.8 dist, 1.2 dist) in
+ * fp64 (the reference's expression as written; z = shift[b] in parity mode) added to the z coordinate and the centre in fp64, rounded
+ * once.  Outputs: features (B,4,N), one_hot_vectors (B,K), mask_logits (B,N) i64, center (B,3), heading_bin_id (B) i64,
+ * heading_residual (B), size_template_id (B) i64, size_residual (B,3), class_id (B) i64. */
+PVCNN_API int pvcnn_batch_frustum(const float *rows, const void *labels, int label_bytes, const int64_t *offsets, long long W,
+                        const double *item_f64, const float *item_f32, const int64_t *item_i64, int K, int random_flip,
+                        int random_shift, const int64_t *order, long long order_len, const int64_t *cursor, int B, int N,
+                        const int32_t *choices, const double *flip, const double *shift, const int64_t *seed, float *features,
+                        float *one_hot_vectors, int64_t *mask_logits, float *center, int64_t *heading_bin_id,
+                        float *heading_residual, int64_t *size_template_id, float *size_residual, int64_t *class_id, void *stream);
+/* Frustum-KITTI from RGB detections: item_f64 (W) rgb score, item_f32 (W, K + 1) one-hot and rotation angle.  Outputs: features
+ * (B,4,N), one_hot_vectors (B,K), rotation_angle (B) fp32, rgb_score (B) fp64 (default_collate of a Python float). */
+PVCNN_API int pvcnn_batch_frustum_rgb(const float *rows, const int64_t *offsets, long long W, const double *item_f64,
+                            const float *item_f32, int K, const int64_t *order, long long order_len, const int64_t *cursor, int B,
+                            int N, const int32_t *choices, const int64_t *seed, float *features, float *one_hot_vectors,
+                            float *rotation_angle, double *rgb_score, void *stream);
 
 /* ---- 3-nearest-neighbour interpolation ----------------------------------------------------
  * replaces three_nearest_neighbors_interpolate_forward/backward

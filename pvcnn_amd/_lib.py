@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must be imported before the dlopen, see above)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB_PATH = os.path.join(_CSRC, 'libpvcnn_hip.so')
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _vp, _i, _f, _sz, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
 _ll = ctypes.c_longlong
@@ -130,6 +130,11 @@ SIGNATURES = {
     'pvcnn_box_iou_3d': (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     'pvcnn_rotate_iou': (_i, [_vp, _ll, _vp, _ll, _i, _vp, _vp]),
     'pvcnn_box3d_overlap': (_i, [_vp, _vp, _ll, _vp, _vp, _ll, _i, _i, ctypes.c_double, _vp, _vp]),
+    'pvcnn_batch_lds_bytes': (_sz, [_i, _i]),
+    'pvcnn_batch_s3dis': (_i, [_vp, _vp, _i, _vp, _ll, _i, _vp, _ll, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'pvcnn_batch_shapenet': (_i, [_vp, _vp, _i, _vp, _ll, _vp, _vp, _ll, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pvcnn_batch_frustum': (_i, [_vp, _vp, _i, _vp, _ll, _vp, _vp, _vp, _i, _i, _i, _vp, _ll, _vp, _i, _i] + [_vp] * 14),
+    'pvcnn_batch_frustum_rgb': (_i, [_vp, _vp, _ll, _vp, _vp, _i, _vp, _ll, _vp, _i, _i] + [_vp] * 7),
     'pvcnn_frustum_predictions': (_i, [_vp] * 5 + [_i, _i, _i] + [_vp] * 5 + [_ll, _ll, _vp]),
 }
 

@@ -205,6 +205,26 @@ class HipBackend:
                                                   _p(seed) if choices is None else None, _p(selected), None, s), 'mask_select')
         return selected
 
+    # ---- batches assembled on the device (csrc/batch.hip; pvcnn_amd/data.py checks shapes and owns the tensors) ----------------
+    has_batch_assembly = True
+
+    def batch_launch(self, entry, ref, *args):
+        """One pvcnn_batch_* launch on `ref`'s device and torch's current stream.  Tensors among `args` are passed as device
+        pointers (None as NULL) and must live on that device, contiguous; ints go through as they are."""
+        conv = []
+        for a in args:
+            if isinstance(a, torch.Tensor):
+                _dev(a, entry)
+                _shape(a.is_contiguous() and a.device == ref.device, f'{entry}: contiguous tensors on one device expected')
+                conv.append(ctypes.c_void_p(a.data_ptr()))
+            elif a is None:
+                conv.append(ctypes.c_void_p(None))
+            else:
+                conv.append(int(a))
+        _dev(ref, entry)
+        with _Launch(ref) as s:
+            _lib.check(getattr(self.lib, 'pvcnn_' + entry)(*conv, s), entry)
+
     # ---- ball_query.cpp:6-30 ----------------------------------------------------------------
     def ball_query(self, centers_coords, points_coords, radius, num_neighbors):
         _f32(centers_coords, 'centers_coords'); _f32(points_coords, 'points_coords')
