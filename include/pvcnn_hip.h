@@ -47,7 +47,7 @@ extern "C" {
 #define PVCNN_API
 #endif
 
-#define PVCNN_ABI_VERSION 15
+#define PVCNN_ABI_VERSION 16
 #define PVCNN_OK 0
 #define PVCNN_ERR_INVALID_ARGUMENT (-1)
 
@@ -706,6 +706,50 @@ PVCNN_API int pvcnn_frustum_predictions(const float *center, const float *headin
                                         const float *size_scores, const float *size_residuals, int B, int NH, int NS,
                                         const float *bin_centers, const float *size_templates, const double *rotation_angle,
                                         const double *rgb_score, double *table, long long rows, long long step, void *stream);
+
+/* ---- (ABI v16) S3DIS room preparation (csrc/rooms.hip; reference: data/s3dis/prepare_data.py:119-282) --------------------------------
+ * One pass (one block offset) over a room xyzrgb (n, 6) fp64, colours 0..255, is the sequence
+ *   pvcnn_room_extent -> [host reads extent, sizes the (gx, gy) block table] -> pvcnn_room_blocks -> pvcnn_room_cells
+ *   -> [host orders the points by (merged block, cell key)] -> pvcnn_room_plan -> [host reads status: cells, entries, windows, error]
+ *   -> pvcnn_room_fill -> [host orders the entries by (block, shuffle key)] -> pvcnn_room_pack.
+ * extent (6) fp64: per-axis minimum and maximum of the raw coordinates.  num_blocks = gx * gy (dense table, at most 2^24); n at most 2^29.
+ * status (5) int32: [cells, entries, windows, error bits (1: a point outside the block table, 2: a cell index outside 21 bits),
+ * cells that draw from more than 2048 copies (they take the workgroup-per-cell path)].
+ * block_tables (5, num_blocks) int32: points, cells, resampled entries, first entry, first window of every merged block.
+ * workspace: pvcnn_room_workspace_bytes(n, num_blocks) bytes, 8-byte aligned, for every call that takes one.
+ * seed: two int64 words in device memory (the Philox key of the pass).  All fp64 arithmetic is the reference's, one rounding per
+ * operation; minima and counts use integer atomics only: two runs with the same seed are bit-identical. */
+PVCNN_API size_t pvcnn_room_workspace_bytes(long long n, long long num_blocks);
+PVCNN_API int pvcnn_room_extent(const double *xyzrgb, long long n, double *extent, void *workspace, size_t workspace_bytes, void *stream);
+/* point_block (n): dense block key bx * gy + by; block_count, block_target (merge map, step 3), block_rank (the reference's block
+ * number: rank among the occupied blocks), each (num_blocks); zeroes status. */
+PVCNN_API int pvcnn_room_blocks(const double *xyzrgb, long long n, const double *extent, double offset, double block_size, int gx, int gy,
+                                int max_num_points, int *point_block, int *block_count, int *block_target, int *block_rank, int *status,
+                                void *workspace, size_t workspace_bytes, void *stream);
+/* point_block: in the original key, out the merged block; block_min (num_blocks, 3) bit patterns of the fp64 minima; cell_key (n):
+ * (cx, cy, cz) relative to the merged block's minimum, 21 bits each. */
+PVCNN_API int pvcnn_room_cells(const double *xyzrgb, long long n, const double *extent, double grid_size, long long num_blocks,
+                               const int *block_target, int *point_block, unsigned long long *block_min, long long *cell_key, int *status,
+                               void *stream);
+/* sorted_block / sorted_key (n): the points ordered by (merged block, cell key).  point_cell (n), cell_start (n + 1), cell_out (n),
+ * cell_out_start (n): the cell of every sorted point, the first point, the output count and the first entry of every cell. */
+PVCNN_API int pvcnn_room_plan(const int *sorted_block, const long long *sorted_key, long long n, long long num_blocks, int max_num_points,
+                              int *point_cell, int *cell_start, int *cell_out, int *cell_out_start, int *block_tables, int *status,
+                              void *workspace, size_t workspace_bytes, void *stream);
+/* perm (n): the original index of every sorted point.  entry_point / entry_block / entry_key (num_entries): the resampled entries in
+ * (block, cell) order, their merged block and the block shuffle's 63-bit keys. */
+PVCNN_API int pvcnn_room_fill(const int *perm, const int *sorted_block, const int *point_cell, const int *cell_start,
+                              const int *cell_out_start, const int *block_tables, const int *status, long long n, long long num_blocks,
+                              long long num_entries, const long long *seed, int *entry_point, int *entry_block, long long *entry_key,
+                              void *stream);
+/* entry_point / entry_block ordered by (block, shuffle key).  rows (num_entries, 9) fp32, labels_out / indices (num_entries) int32
+ * (labels and labels_out may both be NULL), offsets (num_windows + 1) int64, window_block (num_windows) int32; block_minxy
+ * (num_blocks, 2) is scratch for the per-block minima over the resampled entries. */
+PVCNN_API int pvcnn_room_pack(const double *xyzrgb, const int *labels, long long n, const double *extent, double half_block,
+                              const int *entry_point, const int *entry_block, long long num_entries, long long num_blocks,
+                              int max_num_points, long long num_windows, const int *block_tables, const int *block_rank,
+                              unsigned long long *block_minxy, float *rows, int *labels_out, int *indices, long long *offsets,
+                              int *window_block, void *stream);
 
 #ifdef __cplusplus
 }

@@ -16,10 +16,11 @@ import torch  # noqa: F401  (must be imported before the dlopen, see above)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB_PATH = os.path.join(_CSRC, 'libpvcnn_hip.so')
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _vp, _i, _f, _sz, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
 _ll = ctypes.c_longlong
+_d = ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/pvcnn_hip.h one to one
 SIGNATURES = {
@@ -136,6 +137,13 @@ SIGNATURES = {
     'pvcnn_batch_frustum': (_i, [_vp, _vp, _i, _vp, _ll, _vp, _vp, _vp, _i, _i, _i, _vp, _ll, _vp, _i, _i] + [_vp] * 14),
     'pvcnn_batch_frustum_rgb': (_i, [_vp, _vp, _ll, _vp, _vp, _i, _vp, _ll, _vp, _i, _i] + [_vp] * 7),
     'pvcnn_frustum_predictions': (_i, [_vp] * 5 + [_i, _i, _i] + [_vp] * 5 + [_ll, _ll, _vp]),
+    'pvcnn_room_workspace_bytes': (_sz, [_ll, _ll]),
+    'pvcnn_room_extent': (_i, [_vp, _ll, _vp, _vp, _sz, _vp]),
+    'pvcnn_room_blocks': (_i, [_vp, _ll, _vp, _d, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pvcnn_room_cells': (_i, [_vp, _ll, _vp, _d, _ll, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pvcnn_room_plan': (_i, [_vp, _vp, _ll, _ll, _i] + [_vp] * 6 + [_vp, _sz, _vp]),
+    'pvcnn_room_fill': (_i, [_vp] * 7 + [_ll, _ll, _ll] + [_vp] * 5),
+    'pvcnn_room_pack': (_i, [_vp, _vp, _ll, _vp, _d, _vp, _vp, _ll, _ll, _i, _ll] + [_vp] * 9),
 }
 
 _lib = None

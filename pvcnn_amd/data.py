@@ -42,11 +42,15 @@ def _narrowest(labels):
     labels = np.asarray(labels)
     if labels.size == 0:
         return labels.astype(np.uint8)
-    lo, hi = int(labels.min()), int(labels.max())
-    for dt in (np.uint8, np.int16, np.int32):
-        if np.iinfo(dt).min <= lo and hi <= np.iinfo(dt).max:
-            return labels.astype(dt)
-    return labels.astype(np.int64)
+    return labels.astype(_narrowest_name(int(labels.min()), int(labels.max())))
+
+
+def _narrowest_name(lo, hi):
+    """Name (numpy's and torch's) of the narrowest of uint8 / int16 / int32 / int64 that holds [lo, hi]."""
+    for name in ('uint8', 'int16', 'int32'):
+        if np.iinfo(name).min <= lo and hi <= np.iinfo(name).max:
+            return name
+    return 'int64'
 
 
 class _Store:
@@ -206,6 +210,32 @@ class DeviceS3DIS(_Store):
                     data.append(np.array(h5f['data'])); label.append(np.array(h5f['label_seg'])); num.append(np.array(h5f['data_num']))
         return cls(np.concatenate(data), np.concatenate(label), np.concatenate(num), ds.num_points,
                    with_normalized_coords=ds.with_normalized_coords, device=device)
+
+    @classmethod
+    def from_rooms(cls, windows, num_points, with_normalized_coords=True):
+        """From `rooms.prepare_room` results (one `RoomWindows` or a list of them, every one with labels, on one device): the packed
+        tables are concatenated on the device, in list order -- no numpy round trip.  The store equals the one the constructor builds
+        from the same windows' padded h5 arrays."""
+        windows = [windows] if hasattr(windows, 'rows') else list(windows)
+        if not windows:
+            raise ValueError('an empty split cannot be stored')
+        if any(w.labels is None for w in windows):
+            raise ValueError('every room needs labels (prepare_room(xyzrgb, labels))')
+        if int(num_points) < 1:
+            raise ValueError('num_points must be positive')
+        device = windows[0].rows.device
+        if device.type != 'cuda' or any(w.rows.device != device for w in windows):
+            raise RuntimeError('from_rooms needs the windows of every room on one CUDA (HIP) device -- there is no CPU implementation')
+        self = cls.__new__(cls)
+        self.num_points, self.with_normalized_coords, self.device = int(num_points), bool(with_normalized_coords), device
+        counts = torch.cat([w.offsets[1:] - w.offsets[:-1] for w in windows])
+        self.offsets = torch.cat([torch.zeros((1,), dtype=torch.int64, device=device), torch.cumsum(counts, 0)])
+        self.rows = torch.cat([w.rows for w in windows]).contiguous()
+        labels = torch.cat([w.labels for w in windows])
+        self.max_n, lo, hi = (int(v) for v in torch.stack([counts.max(), labels.min(), labels.max()]).tolist())
+        self.labels = labels.to(getattr(torch, _narrowest_name(lo, hi))).contiguous()
+        self._tables = ['rows', 'labels', 'offsets']
+        return self
 
     @property
     def out_channels(self):
