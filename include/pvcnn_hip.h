@@ -751,6 +751,69 @@ PVCNN_API int pvcnn_room_pack(const double *xyzrgb, const int *labels, long long
                               unsigned long long *block_minxy, float *rows, int *labels_out, int *indices, long long *offsets,
                               int *window_block, void *stream);
 
+/* ---- (additive to ABI v16) the KITTI AP evaluation (csrc/kitti_ap.hip, csrc/boxes.hip; reference: evaluate/kitti/utils/eval.py) ---------
+ * All data is ragged per image, described by int64 prefix offsets of I + 1 words: gt_off (ground truths), dt_off (detections), dc_off
+ * (DontCare ground truths) and pair_off (image i holds dt_i x gt_i overlaps: overlaps[pair_off[i] + det * gt_i + gt], the reference's
+ * overlaps[det, gt]).  G / D: all ground truths / detections.  A cell is (class m, difficulty l, min_overlap row k), index
+ * (m * L + l) * K + k; min_overlaps (K, M) fp64, all >= 0.  Names are int32 codes: 0 car, 1 pedestrian, 2 cyclist, 3 van,
+ * 4 person_sitting, 6 tractor, 7 trailer (the lower-cased name), -2 the exact string 'DontCare', -1 anything else; classes are the
+ * reference's 0..7 (5 is 'car' again), difficulties 0..2.
+ * An image may hold at most PVCNN_KITTI_AP_MAX_BOXES ground truths and as many detections: the matching entry points take the
+ * per-image maxima (max_gt, max_dt) from the caller, who built the offsets, and refuse more -- nothing is truncated.
+ * No entry point allocates, synchronises or uses an atomic; every sum has a fixed order: two runs give the same bits. */
+#define PVCNN_KITTI_AP_MAX_BOXES 2048
+#define PVCNN_KITTI_AP_SAMPLE_POINTS 41
+/* pvcnn_image_box_overlap: the reference's image_box_overlap, out (N, K) fp64 over (x1, y1, x2, y2) fp64 boxes (N, 4) and query_boxes
+ * (K, 4), bit-equal to the reference's expression (one rounding per operation).  criterion -1: IoU, 0: inter / area(box),
+ * 1: inter / area(query box), other: the intersection. */
+PVCNN_API int pvcnn_image_box_overlap(const double *boxes, long long N, const double *query_boxes, long long K, int criterion,
+                                      double *out, void *stream);
+/* pvcnn_kitti_ap_bbox_overlaps: the same IoU over the per-image blocks (boxes = detections, query boxes = ground truths); out
+ * (total_pairs) fp64. */
+PVCNN_API int pvcnn_kitti_ap_bbox_overlaps(const double *dt_bbox, const double *gt_bbox, const long long *dt_off, const long long *gt_off,
+                                           const long long *pair_off, long long images, long long total_pairs, double *out,
+                                           void *stream);
+/* pvcnn_kitti_ap_box_overlaps: pvcnn_rotate_iou (boxes and query_boxes NULL) or pvcnn_box3d_overlap over the per-image blocks, by the
+ * same intersection routine; out (total_pairs) fp32.  box_off / query_off: the offsets of the boxes (detections) and the query boxes
+ * (ground truths). */
+PVCNN_API int pvcnn_kitti_ap_box_overlaps(const float *bev_boxes, const double *boxes, const float *bev_query_boxes,
+                                          const double *query_boxes, const long long *box_off, const long long *query_off,
+                                          const long long *pair_off, long long images, long long total_pairs, int criterion, int z_axis,
+                                          double z_center, float *out, void *stream);
+/* pvcnn_kitti_ap_clean: clean_data for every (class, difficulty): ignored_gt (M * L, G) and ignored_det (M * L, D) int8 in {-1, 0, 1},
+ * num_valid_gt (M * L) int64, and dc_index (dc_off[I]) int32: the positions of every image's DontCare ground truths, in order.
+ * gt_occluded / gt_truncated (G) fp64; bboxes (., 4) fp64. */
+PVCNN_API int pvcnn_kitti_ap_clean(const int *gt_name, const double *gt_bbox, const double *gt_occluded, const double *gt_truncated,
+                                   long long G, const int *dt_name, const double *dt_bbox, long long D, const long long *gt_off,
+                                   const long long *dc_off, long long images, const int *classes, int num_classes, const int *difficulties,
+                                   int num_difficulties, signed char *ignored_gt, signed char *ignored_det, int *dc_index,
+                                   long long *num_valid_gt, void *stream);
+/* pvcnn_kitti_ap_match: compute_statistics_jit with compute_fp = False for every (image, cell), one wave each: for each ground truth
+ * in order, the unassigned detection (ignored_det != -1) with overlap > min_overlap and the highest score, the lowest index among
+ * equal scores.  tp_scores (cells, G) fp64: a true positive's score in the slot of its ground truth, -inf in every other slot. */
+PVCNN_API int pvcnn_kitti_ap_match(const double *overlaps, const long long *gt_off, const long long *dt_off, const long long *dc_off,
+                                   const long long *pair_off, long long images, long long G, long long D, int max_gt, int max_dt,
+                                   const signed char *ignored_gt, const signed char *ignored_det, const double *dt_score,
+                                   const double *dt_alpha, const double *gt_alpha, const double *dt_bbox, const double *gt_bbox,
+                                   const int *dc_index, const double *min_overlaps, int num_classes, int num_difficulties,
+                                   int num_min_overlaps, double *tp_scores, void *stream);
+/* pvcnn_kitti_ap_thresholds: get_thresholds per cell on sorted_scores (cells, G): tp_scores sorted descending along G (the -inf slots
+ * last).  thresholds (cells, 41) fp64, zero behind the first counts[cell] entries; counts (cells) int32.  num_valid_gt (cells / K). */
+PVCNN_API int pvcnn_kitti_ap_thresholds(const double *sorted_scores, long long G, const long long *num_valid_gt, int num_cells,
+                                        int num_min_overlaps, double *thresholds, int *counts, void *stream);
+/* pvcnn_kitti_ap_stats: compute_statistics_jit with compute_fp = True for every (image, threshold slot < counts[cell], cell), summed
+ * over the images as fused_compute_statistics does: pr (cells, 41, 4) fp64 = [tp, fp, fn, similarity], zero in the slots at and
+ * behind counts[cell].  metric 0 subtracts the detections in DontCare regions from fp; compute_aos != 0 sums (1 + cos(gt_alpha -
+ * dt_alpha)) / 2 over the true positives.  workspace: pvcnn_kitti_ap_workspace_bytes(images, cells) bytes, 8-byte aligned. */
+PVCNN_API size_t pvcnn_kitti_ap_workspace_bytes(long long images, int num_cells);
+PVCNN_API int pvcnn_kitti_ap_stats(const double *overlaps, const long long *gt_off, const long long *dt_off, const long long *dc_off,
+                                   const long long *pair_off, long long images, long long G, long long D, int max_gt, int max_dt,
+                                   const signed char *ignored_gt, const signed char *ignored_det, const double *dt_score,
+                                   const double *dt_alpha, const double *gt_alpha, const double *dt_bbox, const double *gt_bbox,
+                                   const int *dc_index, const double *min_overlaps, int num_classes, int num_difficulties,
+                                   int num_min_overlaps, const double *thresholds, const int *counts, int metric, int compute_aos,
+                                   double *pr, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

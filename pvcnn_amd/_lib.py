@@ -144,6 +144,14 @@ SIGNATURES = {
     'pvcnn_room_plan': (_i, [_vp, _vp, _ll, _ll, _i] + [_vp] * 6 + [_vp, _sz, _vp]),
     'pvcnn_room_fill': (_i, [_vp] * 7 + [_ll, _ll, _ll] + [_vp] * 5),
     'pvcnn_room_pack': (_i, [_vp, _vp, _ll, _vp, _d, _vp, _vp, _ll, _ll, _i, _ll] + [_vp] * 9),
+    'pvcnn_image_box_overlap': (_i, [_vp, _ll, _vp, _ll, _i, _vp, _vp]),
+    'pvcnn_kitti_ap_bbox_overlaps': (_i, [_vp] * 5 + [_ll, _ll, _vp, _vp]),
+    'pvcnn_kitti_ap_box_overlaps': (_i, [_vp] * 7 + [_ll, _ll, _i, _i, _d, _vp, _vp]),
+    'pvcnn_kitti_ap_clean': (_i, [_vp, _vp, _vp, _vp, _ll, _vp, _vp, _ll, _vp, _vp, _ll, _vp, _i, _vp, _i] + [_vp] * 5),
+    'pvcnn_kitti_ap_match': (_i, [_vp] * 5 + [_ll, _ll, _ll, _i, _i] + [_vp] * 9 + [_i, _i, _i] + [_vp, _vp]),
+    'pvcnn_kitti_ap_thresholds': (_i, [_vp, _ll, _vp, _i, _i, _vp, _vp, _vp]),
+    'pvcnn_kitti_ap_workspace_bytes': (_sz, [_ll, _i]),
+    'pvcnn_kitti_ap_stats': (_i, [_vp] * 5 + [_ll, _ll, _ll, _i, _i] + [_vp] * 9 + [_i, _i, _i] + [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

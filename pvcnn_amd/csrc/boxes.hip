@@ -309,6 +309,33 @@ __device__ __forceinline__ void rbox_corners(const float *__restrict__ r, float 
   }
 }
 
+// criterion of rotate_iou_gpu_eval on one pair: area_q is the query box's (the reference's area1)
+__device__ __forceinline__ double bev_value(double inter, double area_q, double area_b, int criterion) {
+  return criterion == -1 ? safe_ratio(inter, area_q + area_b - inter)
+         : criterion == 0 ? safe_ratio(inter, area_q)
+         : criterion == 1 ? safe_ratio(inter, area_b)
+                          : inter;
+}
+
+// d3_box_overlap_kernel on the fp32 BEV intersection (the reference's rinc), the rest in fp64; (zhi, zlo, vol): a box's height range and
+// volume, `b` the box's and `q` the query box's
+__device__ __forceinline__ double d3_value(double inter, double zhi_b, double zlo_b, double vol_b, double zhi_q, double zlo_q, double vol_q,
+                                           int criterion) {
+  const double rinc = (double)(float)inter;
+  double v = 0.0;
+  if (rinc > 0.0) {
+    const double iw = fmin(zhi_b, zhi_q) - fmax(zlo_b, zlo_q);
+    if (iw > 0.0) {
+      const double area1 = vol_b, area2 = vol_q, inc = iw * rinc;
+      v = criterion == -1 ? safe_ratio(inc, area1 + area2 - inc)
+          : criterion == 0 ? safe_ratio(inc, area1)
+          : criterion == 1 ? safe_ratio(inc, area2)
+                           : inc;
+    }
+  }
+  return v;
+}
+
 struct TileSide {
   float x[4][kBoxTile], y[4][kBoxTile];
   double zhi[kBoxTile], zlo[kBoxTile], vol[kBoxTile];
@@ -364,29 +391,46 @@ __global__ __launch_bounds__(kBoxThreads) void pair_overlap_kernel(const float *
     // the reference evaluates dev_rotate_iou_eval(query_boxes[k], boxes[n]): area1 is the query box's
     double area_q, area_b;
     const double inter = quad_overlap(qx, qy, bx, by, area_q, area_b);
-    double v;
-    if (!kD3) {
-      v = criterion == -1 ? safe_ratio(inter, area_q + area_b - inter)
-          : criterion == 0 ? safe_ratio(inter, area_q)
-          : criterion == 1 ? safe_ratio(inter, area_b)
-                           : inter;
-    } else {
-      // d3_box_overlap_kernel on the fp32 BEV intersection (the reference's rinc), the rest in fp64
-      const double rinc = (double)(float)inter;
-      v = 0.0;
-      if (rinc > 0.0) {
-        const double iw = fmin(sb.zhi[r], sq.zhi[lane]) - fmax(sb.zlo[r], sq.zlo[lane]);
-        if (iw > 0.0) {
-          const double area1 = sb.vol[r], area2 = sq.vol[lane], inc = iw * rinc;
-          v = criterion == -1 ? safe_ratio(inc, area1 + area2 - inc)
-              : criterion == 0 ? safe_ratio(inc, area1)
-              : criterion == 1 ? safe_ratio(inc, area2)
-                               : inc;
-        }
-      }
-    }
+    const double v = !kD3 ? bev_value(inter, area_q, area_b, criterion)
+                          : d3_value(inter, sb.zhi[r], sb.zlo[r], sb.vol[r], sq.zhi[lane], sq.zlo[lane], sq.vol[lane], criterion);
     out[n * K + k] = (float)v;
   }
+}
+
+// ---- the same overlaps over ragged per-image blocks (the KITTI AP evaluation reads only the diagonal blocks of the reference's
+// 50-image N x K parts): image i holds boxes b_off[i] .. b_off[i+1] and query boxes q_off[i] .. q_off[i+1]; its (boxes_i, queries_i)
+// row-major block starts at out[pair_off[i]].  One lane per pair; the image of a pair is found by bisection of pair_off.
+template <bool kD3>
+__global__ __launch_bounds__(kBoxThreads) void segmented_overlap_kernel(const float *__restrict__ bev_b, const double *__restrict__ full_b,
+                                                                       const float *__restrict__ bev_q, const double *__restrict__ full_q,
+                                                                       const long long *__restrict__ b_off, const long long *__restrict__ q_off,
+                                                                       const long long *__restrict__ pair_off, long long images,
+                                                                       long long total, int criterion, int z_axis, double z_center,
+                                                                       float *__restrict__ out) {
+  const long long p = (long long)blockIdx.x * kBoxThreads + threadIdx.x;
+  if (p >= total) return;
+  long long lo = 0, hi = images;                       // the last image with pair_off[i] <= p
+  while (hi - lo > 1) {
+    const long long mid = (lo + hi) >> 1;
+    if (pair_off[mid] <= p) lo = mid; else hi = mid;
+  }
+  const long long nb = b_off[lo + 1] - b_off[lo], nq = q_off[lo + 1] - q_off[lo], r = p - pair_off[lo];
+  if (nq <= 0 || r >= nb * nq) return;
+  const long long n = b_off[lo] + r / nq, k = q_off[lo] + r % nq;
+  float bx[4], by[4], qx[4], qy[4];
+  rbox_corners(bev_b + 5 * n, bx, by);
+  rbox_corners(bev_q + 5 * k, qx, qy);
+  double area_q, area_b;
+  const double inter = quad_overlap(qx, qy, bx, by, area_q, area_b);
+  double v;
+  if (!kD3) {
+    v = bev_value(inter, area_q, area_b, criterion);
+  } else {
+    const double *b = full_b + 7 * n, *q = full_q + 7 * k;
+    v = d3_value(inter, b[z_axis] + b[z_axis + 3] * (1.0 - z_center), b[z_axis] - b[z_axis + 3] * z_center, b[3] * b[4] * b[5],
+                 q[z_axis] + q[z_axis + 3] * (1.0 - z_center), q[z_axis] - q[z_axis + 3] * z_center, q[3] * q[4] * q[5], criterion);
+  }
+  out[p] = (float)v;
 }
 
 // ---- update_predictions (evaluate/kitti/frustum/eval.py:227-244) on the decoded boxes, fp64 ------------------------------------------
@@ -497,6 +541,28 @@ extern "C" int pvcnn_box3d_overlap(const float *bev_boxes, const double *boxes, 
   PVCNN_REQUIRE(z_axis >= 0 && z_axis <= 2, "z_axis must be 0, 1 or 2");
   PVCNN_REQUIRE(N == 0 || K == 0 || (boxes && query_boxes), "null pointer");
   return launch_pair_overlap(bev_boxes, boxes, N, bev_query_boxes, query_boxes, K, criterion, z_axis, z_center, out, stream);
+}
+
+extern "C" int pvcnn_kitti_ap_box_overlaps(const float *bev_boxes, const double *boxes, const float *bev_query_boxes,
+                                           const double *query_boxes, const long long *box_off, const long long *query_off,
+                                           const long long *pair_off, long long images, long long total_pairs, int criterion, int z_axis,
+                                           double z_center, float *out, void *stream) {
+  PVCNN_REQUIRE(images >= 0 && total_pairs >= 0, "bad sizes");
+  PVCNN_REQUIRE(z_axis >= 0 && z_axis <= 2, "z_axis must be 0, 1 or 2");
+  PVCNN_REQUIRE((boxes == nullptr) == (query_boxes == nullptr), "boxes and query_boxes go together");
+  if (images == 0 || total_pairs == 0) return 0;
+  PVCNN_REQUIRE(bev_boxes && bev_query_boxes && box_off && query_off && pair_off && out, "null pointer");
+  const long long blocks = (total_pairs + kBoxThreads - 1) / kBoxThreads;
+  PVCNN_REQUIRE(blocks < (1ll << 31), "too many pairs");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (boxes == nullptr) {
+    hipLaunchKernelGGL(segmented_overlap_kernel<false>, dim3((unsigned)blocks), dim3(kBoxThreads), 0, s, bev_boxes, nullptr,
+                       bev_query_boxes, nullptr, box_off, query_off, pair_off, images, total_pairs, criterion, 0, 0.0, out);
+  } else {
+    hipLaunchKernelGGL(segmented_overlap_kernel<true>, dim3((unsigned)blocks), dim3(kBoxThreads), 0, s, bev_boxes, boxes, bev_query_boxes,
+                       query_boxes, box_off, query_off, pair_off, images, total_pairs, criterion, z_axis, z_center, out);
+  }
+  return check_launch("kitti_ap_box_overlaps");
 }
 
 extern "C" int pvcnn_frustum_predictions(const float *center, const float *heading_scores, const float *heading_residuals,

@@ -1519,6 +1519,112 @@ class HipBackend:
                                                           _p(rotation_angle), _p(rgb_score), _p(table), table.shape[0], int(step), s),
                        'frustum_predictions')
 
+    # ---- the KITTI AP evaluation (csrc/kitti_ap.hip; include/pvcnn_hip.h "the KITTI AP evaluation") ----
+    @staticmethod
+    def _ap_typed(t, name, dtype, numel=None):
+        _dev(t, name)
+        _shape(t.dtype == dtype and t.is_contiguous() and (numel is None or t.numel() == numel),
+               f'kitti_ap: {name} must be a contiguous {dtype} tensor' + ('' if numel is None else f' of {numel} elements'))
+
+    def image_box_overlap(self, boxes, query_boxes, criterion=-1):
+        """(N, K) float64 overlaps of (N, 4) and (K, 4) float64 boxes: the reference's image_box_overlap, bit for bit."""
+        n, k = boxes.shape[0], query_boxes.shape[0]
+        self._ap_typed(boxes, 'boxes', torch.float64, 4 * n); self._ap_typed(query_boxes, 'query_boxes', torch.float64, 4 * k)
+        out = torch.zeros((n, k), dtype=torch.float64, device=boxes.device)
+        with _Launch(boxes) as s:
+            _lib.check(self.lib.pvcnn_image_box_overlap(_p(boxes), n, _p(query_boxes), k, int(criterion), _p(out), s), 'image_box_overlap')
+        return out
+
+    def kitti_ap_overlaps(self, p, metric, z_axis=1, z_center=1.0):
+        """The per-image overlaps[det, gt] blocks of a packed evaluation `p` (kitti._Packed), flat at p.pair_off: float64 for metric 0
+        (2-D boxes), float32 for 1 (BEV) and 2 (3-D)."""
+        dev = p.gt_off.device
+        if metric == 0:
+            out = torch.zeros((p.pairs,), dtype=torch.float64, device=dev)
+            with _Launch(p.gt_off) as s:
+                _lib.check(self.lib.pvcnn_kitti_ap_bbox_overlaps(_p(p.dt_bbox), _p(p.gt_bbox), _p(p.dt_off), _p(p.gt_off), _p(p.pair_off),
+                                                                 p.images, p.pairs, _p(out), s), 'kitti_ap_bbox_overlaps')
+            return out
+        _shape(metric in (1, 2), 'unknown metric')
+        bev_dt, bev_gt, full_dt, full_gt = p.boxes_3d(z_axis)
+        out = torch.zeros((p.pairs,), dtype=torch.float32, device=dev)
+        full = (None, None) if metric == 1 else (full_dt, full_gt)
+        with _Launch(p.gt_off) as s:
+            _lib.check(self.lib.pvcnn_kitti_ap_box_overlaps(_p(bev_dt), _p(full[0]), _p(bev_gt), _p(full[1]), _p(p.dt_off), _p(p.gt_off),
+                                                            _p(p.pair_off), p.images, p.pairs, -1, int(z_axis), float(z_center), _p(out), s),
+                       'kitti_ap_box_overlaps')
+        return out
+
+    def kitti_ap_clean(self, p, classes, difficulties):
+        """clean_data for every (class, difficulty): (ignored_gt (M, L, G) int8, ignored_det (M, L, D) int8, dc_index int32,
+        num_valid_gt (M, L) int64).  classes / difficulties: int32 device tensors."""
+        dev = p.gt_off.device
+        m, l = classes.numel(), difficulties.numel()
+        self._ap_typed(classes, 'classes', torch.int32); self._ap_typed(difficulties, 'difficulties', torch.int32)
+        ignored_gt = torch.zeros((m, l, p.G), dtype=torch.int8, device=dev)
+        ignored_det = torch.zeros((m, l, p.D), dtype=torch.int8, device=dev)
+        dc_index = torch.zeros((p.dontcares,), dtype=torch.int32, device=dev)
+        dc_out = self._ap_some(dc_index)
+        num_valid_gt = torch.zeros((m, l), dtype=torch.int64, device=dev)
+        with _Launch(p.gt_off) as s:
+            _lib.check(self.lib.pvcnn_kitti_ap_clean(_p(p.gt_name), _p(p.gt_bbox), _p(p.gt_occluded), _p(p.gt_truncated), p.G, _p(p.dt_name),
+                                                     _p(p.dt_bbox), p.D, _p(p.gt_off), _p(p.dc_off), p.images, _p(classes), m,
+                                                     _p(difficulties), l, _p(ignored_gt), _p(ignored_det), _p(dc_out), _p(num_valid_gt), s),
+                       'kitti_ap_clean')
+        return ignored_gt, ignored_det, dc_index, num_valid_gt
+
+    @staticmethod
+    def _ap_some(t):
+        """t, or one zero where t is empty: the library refuses a null pointer wherever the sizes alone do not rule a read out."""
+        return t if t.numel() > 0 else torch.zeros((1,), dtype=t.dtype, device=t.device)
+
+    def _ap_args(self, p, overlaps, clean, min_overlaps):
+        ignored_gt, ignored_det, dc_index, _ = clean
+        m, l = ignored_gt.shape[:2]
+        k = min_overlaps.shape[0]
+        self._ap_typed(overlaps, 'overlaps', torch.float64, p.pairs)
+        self._ap_typed(min_overlaps, 'min_overlaps', torch.float64, k * m)
+        self._ap_typed(ignored_gt, 'ignored_gt', torch.int8, m * l * p.G); self._ap_typed(ignored_det, 'ignored_det', torch.int8, m * l * p.D)
+        self._ap_typed(dc_index, 'dc_index', torch.int32, p.dontcares)
+        overlaps, dc_index = self._ap_some(overlaps), self._ap_some(dc_index)
+        return (_p(overlaps), _p(p.gt_off), _p(p.dt_off), _p(p.dc_off), _p(p.pair_off), p.images, p.G, p.D, p.max_gt, p.max_dt,
+                _p(ignored_gt), _p(ignored_det), _p(p.dt_score), _p(p.dt_alpha), _p(p.gt_alpha), _p(p.dt_bbox), _p(p.gt_bbox), _p(dc_index),
+                _p(min_overlaps), m, l, k), (m, l, k)
+
+    def kitti_ap_match(self, p, overlaps, clean, min_overlaps):
+        """Matching pass 1 for every (image, class, difficulty, min_overlap row): tp_scores (M, L, K, G) float64, a true positive's
+        score in the slot of its ground truth and -inf elsewhere.  overlaps: float64, flat at p.pair_off; min_overlaps (K, M)."""
+        args, cells = self._ap_args(p, overlaps, clean, min_overlaps)
+        tp_scores = torch.full(cells + (p.G,), float('-inf'), dtype=torch.float64, device=overlaps.device)
+        with _Launch(p.gt_off) as s:
+            _lib.check(self.lib.pvcnn_kitti_ap_match(*args, _p(tp_scores), s), 'kitti_ap_match')
+        return tp_scores
+
+    def kitti_ap_thresholds(self, tp_scores, num_valid_gt):
+        """get_thresholds per cell: (thresholds (M, L, K, 41) float64, counts (M, L, K) int32), left on the device."""
+        m, l, k, g = tp_scores.shape
+        self._ap_typed(tp_scores, 'tp_scores', torch.float64); self._ap_typed(num_valid_gt, 'num_valid_gt', torch.int64, m * l)
+        ordered = torch.sort(tp_scores, dim=-1, descending=True).values.contiguous()
+        thresholds = torch.zeros((m, l, k, 41), dtype=torch.float64, device=tp_scores.device)
+        counts = torch.zeros((m, l, k), dtype=torch.int32, device=tp_scores.device)
+        with _Launch(tp_scores) as s:
+            _lib.check(self.lib.pvcnn_kitti_ap_thresholds(_p(ordered), g, _p(num_valid_gt), m * l * k, k, _p(thresholds), _p(counts), s),
+                       'kitti_ap_thresholds')
+        return thresholds, counts
+
+    def kitti_ap_stats(self, p, overlaps, clean, min_overlaps, thresholds, counts, metric, compute_aos):
+        """Matching pass 2 at every threshold slot, summed over the images: pr (M, L, K, 41, 4) float64 = [tp, fp, fn, similarity]."""
+        args, cells = self._ap_args(p, overlaps, clean, min_overlaps)
+        n = cells[0] * cells[1] * cells[2]
+        self._ap_typed(thresholds, 'thresholds', torch.float64, n * 41); self._ap_typed(counts, 'counts', torch.int32, n)
+        pr = torch.zeros(cells + (41, 4), dtype=torch.float64, device=overlaps.device)
+        nbytes = self.lib.pvcnn_kitti_ap_workspace_bytes(p.images, n)
+        workspace = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=overlaps.device)
+        with _Launch(p.gt_off) as s:
+            _lib.check(self.lib.pvcnn_kitti_ap_stats(*args, _p(thresholds), _p(counts), int(metric), int(bool(compute_aos)), _p(pr),
+                                                     _p(workspace), nbytes, s), 'kitti_ap_stats')
+        return pr
+
 
 class _WeightBank:
     """Persistent f16x2 image pairs of registered weights (HipBackend.weight_bank_*).  An entry is keyed by (kind, data pointer,
