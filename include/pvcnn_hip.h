@@ -47,7 +47,7 @@ extern "C" {
 #define PVCNN_API
 #endif
 
-#define PVCNN_ABI_VERSION 16
+#define PVCNN_ABI_VERSION 17
 #define PVCNN_OK 0
 #define PVCNN_ERR_INVALID_ARGUMENT (-1)
 
@@ -314,8 +314,11 @@ PVCNN_API int pvcnn_conv3d_weight_split(const float *w, int Co, int Ci, int for_
 PVCNN_API int pvcnn_conv3d_weight_split_pair(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, void *stream);
 PVCNN_API size_t pvcnn_conv3d_fwd_split_stats_parts(int B, int Co, int R, int nsplit);
 /* (ABI v8) which launch shape pvcnn_conv3d_fwd_split takes for this problem: (voxels per workgroup tile) << 8 | weight rows per
- * tile (64, or 32 for the half-height tile of layers with Co <= 32 at R = 32).  Pure function of the sizes; for tests and tools
- * that have to prove a given tile ran (tests/test_gpu_parity_as_benched.py). */
+ * tile (64, or 32 for the half-height tile of layers with Co <= 32 at R = 32).  Pure function of the sizes and the process's
+ * switches; for tests and tools that have to prove a given tile ran (tests/test_gpu_parity_as_benched.py).
+ * (ABI v17) the value is read off the launch's own plan (csrc/route.h): where the persistent kernel runs (f16x2, R = 32 -- R = 16 with
+ * PVCNN_CONV_WIDE16=1 --, Ci % 16 == 0, Ci >= 32, Co > 32, tensors below 4 GiB) it reports that kernel's 4 x 4 x R tile, 512 voxels
+ * (256 at R = 16), and the two-workgroup kernel's tile under PVCNN_CONV_WIDE=0; before, the two-workgroup tile in either case. */
 PVCNN_API int pvcnn_conv3d_fwd_split_route(int B, int Ci, int Co, int R, int nsplit);
 PVCNN_API int pvcnn_absmax_bits(const float *x, size_t n, void *out, void *stream);
 PVCNN_API size_t pvcnn_absmax_tiles_count(int B, long L, int seg);      /* 1 + T words */
@@ -377,6 +380,9 @@ PVCNN_API size_t pvcnn_pwconv_weight_split_bytes(int Co, int Ci, int for_bwd_dat
 PVCNN_API int pvcnn_pwconv_weight_split(const float *w, int Co, int Ci, int for_bwd_data, int nsplit, void *wts, void *stream);
 PVCNN_API int pvcnn_pwconv_weight_split_pair(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, void *stream);
 PVCNN_API size_t pvcnn_pwconv_fwd_split_stats_parts(int B, int N);
+/* (ABI v17) the twin of pvcnn_conv3d_fwd_split_route: the weight rows per workgroup item of the launch pvcnn_pwconv_fwd_split takes
+ * for a 16-byte aligned x: 64 or 128, and 256 or 512 where the persistent kernel runs (PVCNN_PW_WIDE=0: never; =2: never 512). */
+PVCNN_API int pvcnn_pwconv_fwd_split_route(int B, int K, int M, int N, int nsplit);
 PVCNN_API int pvcnn_pwconv_fwd_split(const float *x, const void *wts, const float *bias, int B, int K, int M, int N, int nsplit,
                            const void *x_absmax, int amax_seg /* 0 | 256 */, float *y, float *stats_part, void *stream);
 /* Backward-weight of the 1x1 convolution in f16x2 (csrc/pointwise_wgrad_f16.hip), N % 4 == 0 (workspace_bytes returns 0 otherwise:

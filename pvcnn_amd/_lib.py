@@ -16,7 +16,7 @@ import torch  # noqa: F401  (must be imported before the dlopen, see above)
 
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB_PATH = os.path.join(_CSRC, 'libpvcnn_hip.so')
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _vp, _i, _f, _sz, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
 _ll = ctypes.c_longlong
@@ -77,6 +77,7 @@ SIGNATURES = {
     'pvcnn_pwconv_weight_split': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     'pvcnn_pwconv_weight_split_pair': (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     'pvcnn_pwconv_fwd_split_stats_parts': (_sz, [_i, _i]),
+    'pvcnn_pwconv_fwd_split_route': (_i, [_i, _i, _i, _i, _i]),
     'pvcnn_pwconv_fwd_split': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'pvcnn_pwconv_bwd_weight_f16_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'pvcnn_pwconv_bwd_weight_f16': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),

@@ -1,8 +1,10 @@
-// api.hip -- version / error reporting of libpvcnn_hip.so (see include/pvcnn_hip.h).
+// api.hip -- version / error reporting of libpvcnn_hip.so (see include/pvcnn_hip.h) and the reader of its process-wide switches.
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "common.h"
+#include "switches.h"
 
 namespace pvcnn {
 
@@ -20,6 +22,21 @@ int check_launch(const char *what) {
   if (e == hipSuccess) return 0;
   set_error("%s: kernel launch failed: %s", what, hipGetErrorString(e));
   return static_cast<int>(e);
+}
+
+const Switches &switches() {
+  static const Switches sw = [] {
+    auto first = [](const char *name) { const char *e = getenv(name); return e ? e[0] : '\0'; };
+    Switches s;
+    s.conv_wide = first("PVCNN_CONV_WIDE") != '0';
+    s.conv_wide16 = first("PVCNN_CONV_WIDE16") == '1';
+    const char pw = first("PVCNN_PW_WIDE");
+    s.pw_wide = pw == '0' ? 0 : pw == '2' ? 2 : 1;
+    s.wgrad_pp = first("PVCNN_WGRAD_PP") != '0';
+    s.gather_pipe = first("PVCNN_GATHER_PIPE") != '0';
+    return s;
+  }();
+  return sw;
 }
 
 }  // namespace pvcnn

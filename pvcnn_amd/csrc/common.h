@@ -5,6 +5,7 @@
 #include <stddef.h>
 
 #include "../../include/pvcnn_hip.h"
+#include "switches.h"
 
 namespace pvcnn {
 

@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include <string.h>
+#include "route.h"
 #include "split16.h"
 
 namespace pvcnn {
@@ -1217,8 +1218,8 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_f16_wide_kernel(const flo
           float2 t = stat_lds[tid_e];
 #pragma unroll
           for (int w = 1; w < 4; ++w) { t.x += stat_lds[w * kCoTileB + tid_e].x; t.y += stat_lds[w * kCoTileB + tid_e].y; }
-          // stats_parts = the slots per channel the caller allocated (pvcnn_conv3d_fwd_split_stats_parts: the two-workgroup
-          // kernel's tile count -- twice n_tiles where a small batch takes its 256-voxel tile): the surplus slots are zeros
+          // stats_parts = the slots per channel the caller allocated (route.h: ConvFwdPlan::stats_slots, the two-workgroup kernel's
+          // tile count -- twice n_tiles = tiles_written where a small batch takes its 256-voxel tile): the surplus slots are zeros
           stats_part[(size_t)(co0 + tid_e) * stats_parts + cur.stat_slot] = t;
           if (stats_parts > n_tiles) stats_part[(size_t)(co0 + tid_e) * stats_parts + n_tiles + cur.stat_slot] = make_float2(0.0f, 0.0f);
         }
@@ -1229,26 +1230,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_f16_wide_kernel(const flo
   }
 }
 
-// Workgroup tile and staging path.  Vector staging (whole z rows as 16-byte loads) needs R % 4 == 0 and a tile that spans z:
-// tz = 8 / 16 / 32 for R <= 8 / 16 / 32.  At 16 < R <= 32 a 512-voxel tile (a wave owns 64 channels x 128 voxels: every weight
-// fragment feeds four MFMA column blocks, the halo overhead drops from 3.0x to 2.25x) when that still leaves two workgroups for
-// every CU; the six-product bf16x3 mode has neither the registers nor the LDS for it.  (Measured, (16,64,64,32^3), f16x2:
-// scalar staging 0.354 ms, vector 0.320 ms, vector + 512-voxel tile 0.309 ms; a (4,8,16) tile at R = 16 spills and loses.)
-struct SplitTile { int tx, ty, tz; bool vec; };
-static SplitTile split_tiles(int B, int Co, int R, int nsplit) {
-  const bool vec = R % 4 == 0 && R <= 32;
-  if (R <= 8) {  // tiny grids (PVCNN++ at R = 8, B = 8: 16 tiles of 256 voxels per 64 channels): halve the tile while the chip is not full
-    const long per = (long)B * ceil_div(R, 8) * ceil_div(Co, kCoTileB);
-    // (measured, f16x2 forward, (8,128,128,8): 38.5 -> 28.4 us; (8,256,256,8): 71.3 -> 61.6; PVCNN++ step 574.7 -> 581.0 clouds/s in one call)
-    if (per * ceil_div(R, 2) < kNumCU) return SplitTile{1, 8, 8, vec};
-    return per * ceil_div(R, 4) < kNumCU ? SplitTile{2, 8, 8, vec} : SplitTile{4, 8, 8, vec};
-  }
-  if (!vec) return {4, 4, 16, false};
-  if (R <= 16)   // too few 256-voxel tiles to give every SIMD two waves (R = 16, B = 16: 256 per 64 channels): halve them
-    return (long)B * ceil_div(R, 4) * ceil_div(R, 4) * ceil_div(Co, kCoTileB) < 768 ? SplitTile{2, 4, 16, true} : SplitTile{4, 4, 16, true};
-  const bool big = nsplit != 3 && (long)B * ceil_div(R, 4) * ceil_div(R, 4) * ceil_div(Co, kCoTileB) >= 512;
-  return big ? SplitTile{4, 4, 32, true} : SplitTile{2, 4, 32, true};
-}
+static_assert(route::kNumCU == kNumCU && route::kCoTileB == kCoTileB && route::kKc == kKc, "route.h plans with this file's constants");
 
 template <int TX, int TY>
 static int launch_igemm_f16_pipe(const float *x, const uint16_t *wts, const float *bias, float *y, int B, int Ci, int Co, int R, hipStream_t s,
@@ -1425,18 +1407,14 @@ extern "C" int pvcnn_conv3d_weight_split_pair_batch_bf16(const void *table, int 
 
 extern "C" size_t pvcnn_conv3d_fwd_split_stats_parts(int B, int Co, int R, int nsplit) {
   if (B <= 0 || Co <= 0 || R <= 0) return 0;
-  const SplitTile t = split_tiles(B, Co, R, nsplit);
-  return (size_t)B * ceil_div(R, t.tx) * ceil_div(R, t.ty) * ceil_div(R, t.tz);
+  return route::conv3d_fwd_split_plan(B, /* Ci: no part in the slot count */ 0, Co, R, nsplit, switches()).stats_slots;
 }
 
-// the launch shape conv3d_fwd_split_impl's dispatch below takes: (voxels per tile) << 8 | weight rows per tile
+// the launch shape conv3d_fwd_split_impl below takes: (voxels per tile) << 8 | weight rows per tile
 extern "C" int pvcnn_conv3d_fwd_split_route(int B, int Ci, int Co, int R, int nsplit) {
   if (B <= 0 || Ci <= 0 || Co <= 0 || R <= 0 || nsplit < 1 || nsplit > 3) return 0;
-  const SplitTile t = split_tiles(B, Co, R, nsplit);
-  int tx = t.tx, ty = t.ty, tz = t.tz, rows = kCoTileB;
-  if (t.tz == 16 && t.vec && t.tx == 2 && nsplit == 2 && Ci % kKc == 0) { tx = 2; ty = 4; tz = 16; }    // the pipelined kernel: same tile
-  if (t.vec && t.tz == 32 && Co <= 32 && nsplit == 2) rows = 32;
-  return ((tx * ty * tz) << 8) | rows;
+  const route::ConvFwdPlan p = route::conv3d_fwd_split_plan(B, Ci, Co, R, nsplit, switches());
+  return ((p.tx * p.ty * p.tz) << 8) | p.rows;
 }
 
 // y = conv3d(x, w) + bias with the pre-split weights of pvcnn_conv3d_weight_split (forward layout: Ci, Co as given; backward-data:
@@ -1454,71 +1432,63 @@ static int conv3d_fwd_split_impl(const float *x, const void *wts, const float *b
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint16_t *w16 = static_cast<const uint16_t *>(wts);
   float2 *sp = reinterpret_cast<float2 *>(stats_part);
-  const SplitTile t = split_tiles(B, Co, R, nsplit);
-  PVCNN_REQUIRE(!t.vec || aligned16(x), "x must be 16-byte aligned");
+  const route::ConvFwdPlan p = route::conv3d_fwd_split_plan(B, Ci, Co, R, nsplit, switches());
+  PVCNN_REQUIRE(!p.vec || aligned16(x), "x must be 16-byte aligned");
   const uint32_t *am = static_cast<const uint32_t *>(x_absmax);
   const int *wexp = nsplit == 2 ? reinterpret_cast<const int *>(static_cast<const char *>(wts) + weight_image_bytes(Ci, Co, 2)) : nullptr;
 #define PVCNN_IGEMM(NS, TX, TY, TZ, VEC) launch_igemm_bf16<NS, TX, TY, TZ, VEC>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg)
 #define PVCNN_IGEMM_NS(TX, TY, TZ, VEC) (nsplit == 3 ? PVCNN_IGEMM(3, TX, TY, TZ, VEC) : nsplit == 2 ? PVCNN_IGEMM(2, TX, TY, TZ, VEC) : PVCNN_IGEMM(1, TX, TY, TZ, VEC))
-#define PVCNN_IGEMM_BIG(TX, TY, TZ) (nsplit == 2 ? PVCNN_IGEMM(2, TX, TY, TZ, true) : PVCNN_IGEMM(1, TX, TY, TZ, true))
-  // round 6: R = 32 / 16, whole 16-channel chunks: the persistent one-workgroup-per-CU kernel (conv3d_igemm_f16_wide_kernel)
-  static const bool wide_on = [] { const char *e = getenv("PVCNN_CONV_WIDE"); return !(e && e[0] == '0'); }();
-  // (R = 16: measured -- tools/calls_r06/r06_call10: 6 .. 9 % faster per launch than conv3d_igemm_f16_pipe_kernel, 44.8 / 80.2 / 144.0 us
-  //  against 47.6 / 87.5 / 156.3 at 64 -> 64 / 64 -> 128 / 128 -> 128, but nothing in the step: 6.076 / 6.083 ms with, 6.066 / 6.060
-  //  without -- one item per workgroup at Co = 64, nothing for the persistence to hide.  Opt-in: PVCNN_CONV_WIDE16=1; tested either way)
-  static const bool wide16_on = [] { const char *e = getenv("PVCNN_CONV_WIDE16"); return e && e[0] == '1'; }();
-  if (wide_on && nsplit == 2 && (R == 32 || (R == 16 && wide16_on)) && Co > 32 && Ci % kKc == 0 && Ci >= 2 * kKc &&
-      (long)B * std::max(Ci, Co) * R * R * R * 4 < 0xffffffffL) {
-    const int cotiles = ceil_div(Co, kCoTileB), n_tiles = B * (R / 4) * (R / 4);
-    const long per_xcd = (long)((n_tiles + 7) / 8) * cotiles;
-    const unsigned grid = 8u * (unsigned)std::min<long>(kNumCU / 8, per_xcd);
-    const unsigned xb = (unsigned)((size_t)B * Ci * R * R * R * 4), wb = (unsigned)weight_image_bytes(Ci, Co, 2);
-    const int parts = (int)pvcnn_conv3d_fwd_split_stats_parts(B, Co, R, nsplit);
+#define PVCNN_IGEMM_VEC(TX, TY, TZ) (p.vec ? PVCNN_IGEMM_NS(TX, TY, TZ, true) : PVCNN_IGEMM_NS(TX, TY, TZ, false))
+  switch (p.kernel) {
+    case route::ConvKernel::Wide: {
+      const unsigned xb = (unsigned)((size_t)B * Ci * R * R * R * 4), wb = (unsigned)weight_image_bytes(Ci, Co, 2);
 #define PVCNN_CW_LAUNCH(TZV, ABV)                                                                                                    \
-    do {                                                                                                                               \
-      auto kw = conv3d_igemm_f16_wide_kernel<TZV, ABV>;                                                                                \
-      const int lds_bytes = (int)CwGeom<TZV>::LDS;                                                                                     \
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kw), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);   \
-      if (e != hipSuccess) { set_error("conv3d(wide): LDS attribute: %s", hipGetErrorString(e)); return (int)e; }                      \
-      hipLaunchKernelGGL(kw, dim3(grid), dim3(256), lds_bytes, s, x, w16, bias, y, Ci, Co, B, sp, am, wexp, amax_seg, xb, wb, parts);   \
-    } while (0)
+      do {                                                                                                                             \
+        auto kw = conv3d_igemm_f16_wide_kernel<TZV, ABV>;                                                                              \
+        const int lds_bytes = (int)CwGeom<TZV>::LDS;                                                                                   \
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kw), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
+        if (e != hipSuccess) { set_error("conv3d(wide): LDS attribute: %s", hipGetErrorString(e)); return (int)e; }                    \
+        hipLaunchKernelGGL(kw, dim3(p.grid_x), dim3(256), lds_bytes, s, x, w16, bias, y, Ci, Co, B, sp, am, wexp, amax_seg, xb, wb,    \
+                           (int)p.stats_slots);                                                                                        \
+      } while (0)
 #ifdef PVCNN_ABLATE
-    const char *ab_env = getenv("PVCNN_CONV_ABLATE");
-    const int ab = ab_env ? atoi(ab_env) : 0;
-    if (R == 32) {
-      switch (ab) {
-        case 1: PVCNN_CW_LAUNCH(32, 1); break;
-        case 2: PVCNN_CW_LAUNCH(32, 2); break;
-        case 4: PVCNN_CW_LAUNCH(32, 4); break;
-        case 8: PVCNN_CW_LAUNCH(32, 8); break;
-        case 16: PVCNN_CW_LAUNCH(32, 16); break;
-        case 31: PVCNN_CW_LAUNCH(32, 31); break;
-        default: PVCNN_CW_LAUNCH(32, 0);
+      const char *ab_env = getenv("PVCNN_CONV_ABLATE");
+      const int ab = ab_env ? atoi(ab_env) : 0;
+      if (R == 32) {
+        switch (ab) {
+          case 1: PVCNN_CW_LAUNCH(32, 1); break;
+          case 2: PVCNN_CW_LAUNCH(32, 2); break;
+          case 4: PVCNN_CW_LAUNCH(32, 4); break;
+          case 8: PVCNN_CW_LAUNCH(32, 8); break;
+          case 16: PVCNN_CW_LAUNCH(32, 16); break;
+          case 31: PVCNN_CW_LAUNCH(32, 31); break;
+          default: PVCNN_CW_LAUNCH(32, 0);
+        }
+      } else {
+        switch (ab) {
+          case 31: PVCNN_CW_LAUNCH(16, 31); break;
+          default: PVCNN_CW_LAUNCH(16, 0);
+        }
       }
-    } else {
-      switch (ab) {
-        case 31: PVCNN_CW_LAUNCH(16, 31); break;
-        default: PVCNN_CW_LAUNCH(16, 0);
-      }
-    }
 #else
-    if (R == 32) PVCNN_CW_LAUNCH(32, 0); else PVCNN_CW_LAUNCH(16, 0);
+      if (R == 32) PVCNN_CW_LAUNCH(32, 0); else PVCNN_CW_LAUNCH(16, 0);
 #endif
 #undef PVCNN_CW_LAUNCH
-    return check_launch("conv3d_igemm_f16_wide");
+      return check_launch("conv3d_igemm_f16_wide");
+    }
+    case route::ConvKernel::Pipe:
+      return launch_igemm_f16_pipe<2, 4>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg);
+    case route::ConvKernel::IgemmCo32:
+      return p.tx == 4 ? launch_igemm_bf16<2, 4, 4, 32, true, true>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg)
+                       : launch_igemm_bf16<2, 2, 4, 32, true, true>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg);
+    case route::ConvKernel::Igemm:
+      break;
   }
-  if (t.tz == 8 && t.tx == 1) return t.vec ? PVCNN_IGEMM_NS(1, 8, 8, true) : PVCNN_IGEMM_NS(1, 8, 8, false);
-  if (t.tz == 8 && t.tx == 2) return t.vec ? PVCNN_IGEMM_NS(2, 8, 8, true) : PVCNN_IGEMM_NS(2, 8, 8, false);
-  if (t.tz == 8) return t.vec ? PVCNN_IGEMM_NS(4, 8, 8, true) : PVCNN_IGEMM_NS(4, 8, 8, false);
-  if (!t.vec) return PVCNN_IGEMM_NS(4, 4, 16, false);
-  // the pipelined 128-voxel kernel (f16x2 only).  Round 3, 64 -> 64 at 16^3 x 16: see profiles/ab/r03u_convbench.jsonl
-  if (t.tz == 16 && t.tx == 2 && nsplit == 2 && Ci % kKc == 0) return launch_igemm_f16_pipe<2, 4>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg);
-  if (t.tz == 16) return t.tx == 2 ? PVCNN_IGEMM_NS(2, 4, 16, true) : PVCNN_IGEMM_NS(4, 4, 16, true);
-  if (Co <= 32 && nsplit == 2)     // a 32-row weight tile: no MFMAs on the padded half (f16x2, the default arithmetic, only)
-    return t.tx == 4 ? launch_igemm_bf16<2, 4, 4, 32, true, true>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg)
-                     : launch_igemm_bf16<2, 2, 4, 32, true, true>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg);
-  return t.tx == 4 ? PVCNN_IGEMM_BIG(4, 4, 32) : PVCNN_IGEMM_NS(2, 4, 32, true);
-#undef PVCNN_IGEMM_BIG
+  if (p.tz == 8) return p.tx == 1 ? PVCNN_IGEMM_VEC(1, 8, 8) : p.tx == 2 ? PVCNN_IGEMM_VEC(2, 8, 8) : PVCNN_IGEMM_VEC(4, 8, 8);
+  if (p.tz == 16) return !p.vec ? PVCNN_IGEMM_NS(4, 4, 16, false) : p.tx == 2 ? PVCNN_IGEMM_NS(2, 4, 16, true) : PVCNN_IGEMM_NS(4, 4, 16, true);
+  if (p.tx == 2) return PVCNN_IGEMM_NS(2, 4, 32, true);
+  return nsplit == 2 ? PVCNN_IGEMM(2, 4, 4, 32, true) : PVCNN_IGEMM(1, 4, 4, 32, true);      // (the 512-voxel tile: never bf16x3)
+#undef PVCNN_IGEMM_VEC
 #undef PVCNN_IGEMM_NS
 #undef PVCNN_IGEMM
 }

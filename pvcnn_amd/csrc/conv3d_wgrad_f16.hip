@@ -702,7 +702,7 @@ static int launch_wgrad_f16(const float *x, const float *gy, const uint32_t *xa,
   uint32_t *maxima = reinterpret_cast<uint32_t *>(gb_part + w.gb_floats - 4);
   const long x_words = x_seg > 0 ? (long)B * R * R : 0L, gy_words = gy_seg > 0 ? (long)B * R * R : 0L;
   const bool pack = 3 * Ci <= kWgCi && (R == 32 || R == 16);     // (instantiated for the grids a network's first layer has)
-  static const bool pingpong = [] { const char *e = getenv("PVCNN_WGRAD_PP"); return !(e && e[0] == '0'); }();   // 0: the kernel of rounds 3-5
+  const bool pingpong = switches().wgrad_pp;                     // PVCNN_WGRAD_PP=0: the kernel of rounds 3-5
   auto k = pack ? conv3d_wgrad_f16_kernel<R, (R == 32 || R == 16)> : conv3d_wgrad_f16_kernel<R, false>;
   const bool fits = (size_t)std::max(Ci, Co) * R * R * R * 4 < ((size_t)1 << 32) - 64;      // one buffer descriptor per cloud
   if (pingpong && fits) k = pack ? conv3d_wgrad_f16_pp_kernel<R, (R == 32 || R == 16)> : conv3d_wgrad_f16_pp_kernel<R, false>;

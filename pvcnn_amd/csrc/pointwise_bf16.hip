@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include <string.h>
+#include "route.h"
 #include "split16.h"
 
 namespace pvcnn {
@@ -871,7 +872,8 @@ __global__ __launch_bounds__(256, 1) void pw_gemm_f16_wide_kernel(const float *_
   PVCNN_PROBE_END();
 }
 
-static int pb_mb(int M) { return M > 64 ? 4 : 2; }
+using route::pb_mb;
+static_assert(route::kNumCU == kNumCU && route::kPbN == kPbN, "route.h plans with this file's constants");
 
 }  // namespace pvcnn
 
@@ -974,7 +976,13 @@ extern "C" int pvcnn_pwconv_weight_split_pair_batch_bf16(const void *table, int 
 
 extern "C" size_t pvcnn_pwconv_fwd_split_stats_parts(int B, int N) {
   if (B <= 0 || N <= 0) return 0;
-  return (size_t)B * ceil_div(N, kPbN);
+  return route::pwconv_fwd_split_plan(B, /* K, M, nsplit, alignment: no part in the slot count */ 1, 1, N, 2, true, switches()).stats_slots;
+}
+
+// the weight rows per workgroup item of the launch pvcnn_pwconv_fwd_split takes (x 16-byte aligned): 64 / 128, wide kernel 256 / 512
+extern "C" int pvcnn_pwconv_fwd_split_route(int B, int K, int M, int N, int nsplit) {
+  if (B <= 0 || K <= 0 || M <= 0 || N <= 0 || nsplit < 1 || nsplit > 3) return 0;
+  return route::pwconv_fwd_split_plan(B, K, M, N, nsplit, true, switches()).rows;
 }
 
 // y (B,M,N) = W x + bias with the pre-split weights (forward: K = Ci, M = Co; backward-data: x = grad_y, K = Co, M = Ci, bias NULL,
@@ -989,53 +997,28 @@ extern "C" int pvcnn_pwconv_fwd_split(const float *x, const void *wts, const flo
   PVCNN_REQUIRE(x && wts && y && aligned16(wts), "null or misaligned pointer");
   PVCNN_REQUIRE(!stats_part || (reinterpret_cast<uintptr_t>(stats_part) & 7) == 0, "stats_part must be 8-byte aligned");
   PVCNN_REQUIRE((long)N * std::max(K, M) <= 0x7fffffffL, "cloud too large");
-  const int tiles_n = ceil_div(N, kPbN), MB = pb_mb(M);
-  const long tiles_total = (long)B * tiles_n;
-  const long wgs = ((tiles_total + 7) / 8) * 8 * ceil_div(M, 32 * MB);       // tiles padded to the 8 XCDs
-  PVCNN_REQUIRE(wgs <= 0x7fffffffL, "grid too large");
-  const dim3 grid((unsigned)wgs);
+  const route::PwFwdPlan p = route::pwconv_fwd_split_plan(B, K, M, N, nsplit, aligned16(x), switches());
+  PVCNN_REQUIRE(p.grid <= 0x7fffffffL, "grid too large");
+  const dim3 grid((unsigned)p.grid);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const uint16_t *w16 = static_cast<const uint16_t *>(wts);
   float2 *sp = reinterpret_cast<float2 *>(stats_part);
   const uint32_t *am = static_cast<const uint32_t *>(x_absmax);
   const int *wexp = nsplit == 2 ? reinterpret_cast<const int *>(static_cast<const char *>(wts) + pb_image_bytes(K, M, 2)) : nullptr;
-  const bool vec = N % 4 == 0 && N >= 4 && aligned16(x);       // straight-line chunk loop (see the kernel)
-#define PVCNN_PB_LAUNCH_PF(NSV, MBV, PFV)                                                                                            \
-  do {                                                                                                                               \
-    if (vec) hipLaunchKernelGGL((pw_gemm_bf16_kernel<NSV, MBV, PFV, true>), grid, dim3(256), 0, s, x, w16, bias, y, K, M, N, tiles_n, \
-                                (int)tiles_total, sp, am, wexp, amax_seg);                                                           \
-    else hipLaunchKernelGGL((pw_gemm_bf16_kernel<NSV, MBV, PFV, false>), grid, dim3(256), 0, s, x, w16, bias, y, K, M, N, tiles_n,    \
-                            (int)tiles_total, sp, am, wexp, amax_seg);                                                               \
+#define PVCNN_PB_LAUNCH(KERNEL, LDS, ...) \
+  hipLaunchKernelGGL((KERNEL), grid, dim3(256), LDS, s, x, w16, bias, y, K, M, N, p.tiles_n, (int)p.tiles_total, sp, am, wexp, amax_seg, ##__VA_ARGS__)
+#define PVCNN_PB_GEMM(NSV, MBV, PFV)                                                                \
+  do {                                                                                              \
+    if (p.vec) PVCNN_PB_LAUNCH((pw_gemm_bf16_kernel<NSV, MBV, PFV, true>), 0);                         \
+    else PVCNN_PB_LAUNCH((pw_gemm_bf16_kernel<NSV, MBV, PFV, false>), 0);                              \
   } while (0)
-#define PVCNN_PB_LAUNCH(NSV, MBV) PVCNN_PB_LAUNCH_PF(NSV, MBV, 1)
-  // prefetch depth of the wide f16x2 tile, measured (profiles/ab/r03c_pwbench_pf*.jsonl, 1472 -> 512 over 65 536 points): PF = 1 / 2 / 3
-  // = 0.576 / 0.538 / 0.523 ms forward, 1788 / 1820 / 1824 clouds/s in the step; PF = 2 is kept (232 VGPRs; PF = 3 needs 252 of 256)
-  if (nsplit == 3)      { if (MB == 4) PVCNN_PB_LAUNCH(3, 4); else PVCNN_PB_LAUNCH(3, 2); }
-  else if (nsplit == 2) {
-    // measured (profiles/ab/r03k_*, 1472 -> 512 over 65 536 points, forward): round-3 start 0.483 ms; straight-line chunk loop
-    // (VEC) 0.347 ms; + conversion between the MFMAs, one barrier per chunk (pipe kernel) 0.306 ms; the step 1925 -> 2103 -> 2108 clouds/s
-    // round 6: 256 output channels per workgroup, one persistent workgroup per CU (pw_gemm_f16_wide_kernel)
-    static const bool wide_on = [] { const char *e = getenv("PVCNN_PW_WIDE"); return !(e && e[0] == '0'); }();
-    const int mtiles128 = ceil_div(M, 128);
-    if (wide_on && MB == 4 && vec && K % 64 == 0 && N % kPbN == 0 && M >= 256 && mtiles128 % 2 == 0 &&
-        (long)B * std::max(K, M) * N * 4 < 0xffffffffL) {        // (buffer descriptors: 32-bit byte offsets inside a tensor)
-      // 512 x 128 items (4 x 1 waves) where the image has a multiple of four 128-row blocks (PVCNN_PW_WIDE=2: the 256 x 256 items only)
-      static const bool wide4_on = [] { const char *e = getenv("PVCNN_PW_WIDE"); return !(e && e[0] == '2'); }();
-      // (K >= 256: with a handful of steps per item -- 128 -> 1024: eight -- the launch is its epilogues and stores, and the 256 x 256
-      //  items are faster: 79 vs 94 us, tools/calls_r06/r06_call13)
-      const int wmw = (wide4_on && mtiles128 % 4 == 0 && K >= 256) ? 4 : 2;
-      const long turns_local = ((tiles_total + 7) / 8) * (mtiles128 / wmw);      // (a turn = one 256-point tile x one row group)
-      const unsigned wide_grid = 8u * (unsigned)std::min<long>(kNumCU / 8, turns_local);
-#define PVCNN_WIDE_LAUNCH(ABV)                                                                                                      \
-      do {                                                                                                                              \
-        if (wmw == 4)                                                                                                                   \
-          hipLaunchKernelGGL((pw_gemm_f16_wide_kernel<4, ABV>), dim3(wide_grid), dim3(256), WideGeom<4>::LDS, s, x, w16, bias, y, K, M, N,  \
-                             tiles_n, (int)tiles_total, sp, am, wexp, amax_seg, (unsigned)((size_t)B * K * N * 4),                      \
-                             (unsigned)pb_image_bytes(K, M, 2));                                                                        \
-        else                                                                                                                            \
-          hipLaunchKernelGGL((pw_gemm_f16_wide_kernel<2, ABV>), dim3(wide_grid), dim3(256), WideGeom<2>::LDS, s, x, w16, bias, y, K, M, N,  \
-                             tiles_n, (int)tiles_total, sp, am, wexp, amax_seg, (unsigned)((size_t)B * K * N * 4),                      \
-                             (unsigned)pb_image_bytes(K, M, 2));                                                                        \
+  switch (p.kernel) {
+    case route::PwKernel::Wide: {
+      const unsigned xb = (unsigned)((size_t)B * K * N * 4), wb = (unsigned)pb_image_bytes(K, M, 2);
+#define PVCNN_WIDE_LAUNCH(ABV)                                                                      \
+      do {                                                                                          \
+        if (p.wmw == 4) PVCNN_PB_LAUNCH((pw_gemm_f16_wide_kernel<4, ABV>), WideGeom<4>::LDS, xb, wb);  \
+        else PVCNN_PB_LAUNCH((pw_gemm_f16_wide_kernel<2, ABV>), WideGeom<2>::LDS, xb, wb);             \
       } while (0)
 #ifdef PVCNN_ABLATE
       const char *ab_env = getenv("PVCNN_PW_ABLATE");
@@ -1052,17 +1035,18 @@ extern "C" int pvcnn_pwconv_fwd_split(const float *x, const void *wts, const flo
       PVCNN_WIDE_LAUNCH(0);
 #endif
 #undef PVCNN_WIDE_LAUNCH
-    } else if (MB == 4 && vec)
-      hipLaunchKernelGGL(pw_gemm_f16_pipe_kernel<2>, grid, dim3(256), 0, s, x, w16, bias, y, K, M, N, tiles_n, (int)tiles_total, sp, am, wexp,
-                         amax_seg);
-    else if (MB == 4) PVCNN_PB_LAUNCH_PF(2, 4, 2);
-    else PVCNN_PB_LAUNCH(2, 2);
+      break;
+    }
+    case route::PwKernel::Pipe:
+      if (nsplit == 2) PVCNN_PB_LAUNCH((pw_gemm_f16_pipe_kernel<2>), 0); else PVCNN_PB_LAUNCH((pw_gemm_f16_pipe_kernel<1>), 0);
+      break;
+    case route::PwKernel::Gemm:
+      if (nsplit == 3)      { if (p.mb == 4) PVCNN_PB_GEMM(3, 4, 1); else PVCNN_PB_GEMM(3, 2, 1); }
+      else if (nsplit == 2) { if (p.pf == 2) PVCNN_PB_GEMM(2, 4, 2); else PVCNN_PB_GEMM(2, 2, 1); }
+      else                  { if (p.mb == 4) PVCNN_PB_GEMM(1, 4, 1); else PVCNN_PB_GEMM(1, 2, 1); }
+      break;
   }
-  else if (MB == 4 && vec)   // bf16 operands (autocast): the same pipelined structure with one plane
-    hipLaunchKernelGGL(pw_gemm_f16_pipe_kernel<1>, grid, dim3(256), 0, s, x, w16, bias, y, K, M, N, tiles_n, (int)tiles_total, sp, am, wexp,
-                       amax_seg);
-  else                  { if (MB == 4) PVCNN_PB_LAUNCH(1, 4); else PVCNN_PB_LAUNCH(1, 2); }
+#undef PVCNN_PB_GEMM
 #undef PVCNN_PB_LAUNCH
-#undef PVCNN_PB_LAUNCH_PF
   return check_launch("pwconv_fwd_split");
 }

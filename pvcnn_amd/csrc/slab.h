@@ -792,8 +792,7 @@ int launch_gather(const P &p, const float *src, float *dst, int B, int C, int L,
     // generic plan above picks 256-thread single-row slabs, whose 16 points per thread re-derive their corner taps from the
     // coordinates for EVERY channel (a (16,64,4096,16) devoxelization: 25 us for 42 MB, 0.27 of the HBM peak -- latency, not
     // bandwidth).  gather_lds_pipe_rows_kernel: G rows per slab, taps packed once per workgroup, SEQ slabs with the next one in flight.
-    static const bool pipe4 = [] { const char *e = getenv("PVCNN_GATHER_PIPE"); return !(e && e[0] == '0'); }();
-    if (pipe4 && pl.lds && pshift > 0 && vec_ok && J <= 1024 * 4 && J > 1024 && (L >> 2) == 1024 && aligned16(src) && C >= 4) {
+    if (switches().gather_pipe && pl.lds && pshift > 0 && vec_ok && J <= 1024 * 4 && J > 1024 && (L >> 2) == 1024 && aligned16(src) && C >= 4) {
       constexpr int GR = 2;                                   // rows per slab (4 rows spill 70 registers at 1024 threads / 128 VGPRs)
       const int slabs = ceil_div(C, GR);
       const int seq = (int)std::min<long>(8, std::max<long>(1, (long)B * slabs / kNumCU));
@@ -817,9 +816,8 @@ int launch_gather(const P &p, const float *src, float *dst, int B, int C, int L,
   }
   const dim3 grid(ceil_div(ceil_div(C, pl.G), pl.seq), B);
   if constexpr (P::kGridRows) {
-    // software-pipelined single-row-slab variant (see gather_lds_pipe_kernel); PVCNN_GATHER_PIPE=0 opts out (read once per process)
-    static const bool pipe = [] { const char *e = getenv("PVCNN_GATHER_PIPE"); return !(e && e[0] == '0'); }();
-    if (pipe && pl.threads == 1024 && pl.G == 1 && pshift > 0 && vec_ok && J <= 1024 * 4 && (L & 3) == 0 && (L >> 2) <= 1024 * 8 &&
+    // software-pipelined single-row-slab variant (see gather_lds_pipe_kernel); PVCNN_GATHER_PIPE=0 opts out (switches.h)
+    if (switches().gather_pipe && pl.threads == 1024 && pl.G == 1 && pshift > 0 && vec_ok && J <= 1024 * 4 && (L & 3) == 0 && (L >> 2) <= 1024 * 8 &&
         aligned16(src) && (((size_t)L * sizeof(float)) & 15) == 0) {
       auto k = gather_lds_pipe_kernel<P, XF>;
       if (int e = enable_big_lds(k, pl.bytes)) { set_error("%s: LDS attribute: %d", what, e); return e; }

@@ -1,0 +1,29 @@
+// switches.h -- the process-wide kernel switches of libpvcnn_hip.so: one struct, read from the environment ONCE per process, on first
+// use (switches(), api.hip).  Every default is the measured winner; the other values keep the kernel it replaced for the A/B tests.
+// Plain C++: route.h and host-only tools include it.
+//
+//   variable            default   values                                                       measured / tested
+//   PVCNN_CONV_WIDE     on        0: the two-workgroup Conv3d kernels at R = 32                 conv3d_bf16.hip (wide kernel), test_gpu_conv_wide.py
+//   PVCNN_CONV_WIDE16   off       1: the wide Conv3d kernel at R = 16, too (6 .. 9 % per        conv3d_bf16.hip (conv3d_fwd_split_impl), test_gpu_conv_wide.py
+//                                 launch, nothing in the step)
+//   PVCNN_PW_WIDE       1         0: the 128-row 1x1 GEMM; 2: the wide kernel with 256 x 256    pointwise_bf16.hip (pvcnn_pwconv_fwd_split), test_gpu_pw_wide.py
+//                                 items only (no 512 x 128 items)
+//   PVCNN_WGRAD_PP      on        0: the Conv3d backward-weight kernel of rounds 3-5            conv3d_wgrad_f16.hip, profiles/ab/r06_wgrad.md, test_gpu_wgrad_pp.py
+//   PVCNN_GATHER_PIPE   on        0: the generic LDS gather for grid rows (no pipelined         slab.h (launch_gather), test_gpu_gather_pipe.py
+//                                 R = 32 / two-row R = 16 variants)
+// Only the first character of a value is looked at; anything else than the values listed leaves the default.
+#pragma once
+
+namespace pvcnn {
+
+struct Switches {
+  bool conv_wide = true;
+  bool conv_wide16 = false;
+  int pw_wide = 1;
+  bool wgrad_pp = true;
+  bool gather_pipe = true;
+};
+
+const Switches &switches();
+
+}  // namespace pvcnn

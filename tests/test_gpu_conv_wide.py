@@ -2,7 +2,9 @@
 Ci % 16 == 0, Ci >= 32, Co > 32) is BIT-IDENTICAL to the two-workgroup kernel it replaces (PVCNN_CONV_WIDE=0, read once per process:
 two child processes) -- outputs AND the BatchNorm partial sums --, forward and backward-data: several tiles per workgroup (persistence),
 a batch that does not fill the chip, a channel count with a padded last block (Co = 96), per-row scales decades apart (every tile
-must be converted with ITS item's scale while the request streams run a chunk ahead) and a voxelised-cloud input (zero tiles)."""
+must be converted with ITS item's scale while the request streams run a chunk ahead) and a voxelised-cloud input (zero tiles).
+That the two children ran DIFFERENT kernels is read off pvcnn_conv3d_fwd_split_route in each: the persistent kernel's 4 x 4 x R tile
+against the two-workgroup tile, on exactly the launches the rule above sends to the persistent kernel."""
 import os
 import subprocess
 import sys
@@ -20,13 +22,17 @@ sys.path.insert(0, sys.argv[1])
 from pvcnn_amd.modules.functional.backend import HipBackend
 be = HipBackend()
 cases = torch.load(sys.argv[2])
-out = []
+out, routes = [], []
 for x, w, bias, gy in cases:
+    b, ci, r = x.shape[:3]
+    co = w.shape[0]
+    routes.append([be.lib.pvcnn_conv3d_fwd_split_route(b, ci, co, r, 2), be.lib.pvcnn_conv3d_fwd_split_route(b, co, ci, r, 2)])
     x, w, bias, gy = x.cuda(), w.cuda(), bias.cuda(), gy.cuda()
     y, part = be.conv3d_forward_split(x, w, bias, 2, want_stats=True)
     gx = be.conv3d_backward_data_split(gy, w, 2)
     out.append([y.cpu(), part.cpu(), gx.cpu()])
 torch.save(out, sys.argv[3])
+torch.save(routes, sys.argv[3] + '.routes')
 '''
 
 SHAPES = [(16, 64, 64, 32), (3, 32, 96, 32), (1, 48, 64, 32), (20, 64, 128, 32),       # (B, Ci, Co, R)
@@ -48,11 +54,25 @@ def test_the_wide_conv3d_kernel_is_bit_identical_to_the_two_workgroup_kernel(tmp
     torch.save(cases, tmp_path / 'cases.pt')
     script = tmp_path / 'child.py'
     script.write_text(_CHILD)
-    outs = {}
+    outs, routes = {}, {}
     for tag, flag in (('narrow', '0'), ('wide', '1')):
         env = dict(os.environ, PVCNN_CONV_WIDE=flag, PVCNN_CONV_WIDE16=flag)       # (the R = 16 tile is opt-in: measured, no gain in the step)
         subprocess.run([sys.executable, str(script), ROOT, str(tmp_path / 'cases.pt'), str(tmp_path / f'{tag}.pt')], check=True, env=env, timeout=900)
         outs[tag] = torch.load(tmp_path / f'{tag}.pt')
+        routes[tag] = torch.load(tmp_path / f'{tag}.pt.routes')
+    # the children ran different kernels: the route codes ((voxels per tile) << 8 | weight rows) of the forward (Ci -> Co) and the
+    # backward-data (Co -> Ci) launch of every case.  The switched-off child reports the two-workgroup tile, the default child the
+    # persistent kernel's 4 x 4 x R tile exactly where the rule of the docstring holds -- the codes differ there, except where the
+    # two-workgroup tile IS 4 x 4 x R (a batch that fills the chip: the cases compared bit for bit below), and are equal elsewhere
+    for case, (b, ci, co, r) in enumerate(SHAPES):
+        for direction, (k_in, k_out) in enumerate(((ci, co), (co, ci))):
+            wide = k_in % 16 == 0 and k_in >= 32 and k_out > 32
+            blocks = b * (r // 4) ** 2 * ((k_out + 63) // 64)
+            two_wg_voxels = (512 if blocks >= 512 else 256) if r == 32 else (256 if blocks >= 768 else 128)
+            narrow, default = routes['narrow'][case][direction], routes['wide'][case][direction]
+            assert narrow == (two_wg_voxels << 8) | (32 if r == 32 and k_out <= 32 else 64), (SHAPES[case], direction, narrow)
+            assert default == (((16 * r) << 8) | 64 if wide else narrow), (SHAPES[case], direction, default)
+            assert (narrow != default) == (wide and two_wg_voxels != 16 * r), (SHAPES[case], direction, narrow, default)
     for case, (a, b_) in enumerate(zip(outs['narrow'], outs['wide'])):
         b, ci, co, r = SHAPES[case]
         # the two-workgroup kernel takes the same 512-voxel tile (same scale tile, same products in the same order) once the batch

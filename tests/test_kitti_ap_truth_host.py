@@ -95,11 +95,11 @@ def test_thresholds_skip_branch():
 def test_entry_points_are_declared_bound_and_exported():
     from pvcnn_amd import _lib
     text = open(os.path.join(ROOT, 'include', 'pvcnn_hip.h')).read()
-    assert re.search(r'#define\s+PVCNN_ABI_VERSION\s+16\b', text) and _lib.ABI_VERSION == 16
+    assert re.search(r'#define\s+PVCNN_ABI_VERSION\s+17\b', text) and _lib.ABI_VERSION == 17
     assert re.search(r'#define\s+PVCNN_KITTI_AP_MAX_BOXES\s+2048\b', text)
     code = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     lib = _lib.load()
-    assert lib.pvcnn_version() == 16
+    assert lib.pvcnn_version() == 17
     for name in ENTRY_POINTS:
         assert re.search(r'PVCNN_API\s+[\w\s\*]+?\b' + name + r'\s*\(', code), f'{name} not declared'
         assert name in _lib.SIGNATURES, f'{name} not bound'

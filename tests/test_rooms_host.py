@@ -69,7 +69,7 @@ def test_from_rooms_refuses_an_empty_list():
 def test_entry_points_are_declared_and_bound():
     from pvcnn_amd import _lib
     header = open(os.path.join(ROOT, 'include', 'pvcnn_hip.h')).read()
-    assert re.search(r'#define PVCNN_ABI_VERSION 16\b', header) and _lib.ABI_VERSION == 16
+    assert re.search(r'#define PVCNN_ABI_VERSION 17\b', header) and _lib.ABI_VERSION == 17
     lib = _lib.load()
     for name in ENTRY_POINTS:
         assert re.search(r'PVCNN_API\s+\w+\s+' + name + r'\s*\(', header), name
