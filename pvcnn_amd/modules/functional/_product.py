@@ -1,0 +1,142 @@
+"""The three products of a convolution layer -- forward, backward-data, backward-weight with the bias gradient -- written once for
+the two kinds that run on the package's own GEMM kernels: the voxel 3x3x3 Conv3d (functional/conv3d.py) and the SharedMLP 1x1
+convolution (functional/pwconv.py).
+
+`CONV` and `PW` say what differs between the kinds: the canonical tensor views, the amax segmentation, shapes, the extra bar of the
+1x1 backward-weight, and the names of the backend methods and C entry points.  `forward` / `backward` are the body of both autograd
+nodes; HipBackend's shared helpers and its weight bank (functional/backend.py) read the same descriptors.
+
+Names are composed, so grep for the part behind the kind's prefix: `p.entry(lib, 'fwd_split')` is lib.pvcnn_conv3d_fwd_split or
+lib.pvcnn_pwconv_fwd_split, `p.method(be, 'backward_weight_f16')` is be.conv3d_backward_weight_f16 or be.pwconv_backward_weight_f16.
+
+Arithmetic modes (`nsplit`): 0 = fp32 MFMA, 1 = plain bf16 operands (autocast), 2 = f16x2, 3 = bf16x3."""
+from typing import Callable, NamedTuple
+
+from . import _cache, _gradslots
+
+
+class Product(NamedTuple):
+    kind: str                   # the weight bank's name for the kind
+    c: str                      # C entry points are pvcnn_<c>_*, their error labels <c>_*
+    # (B, C, L ...) tensors: L = x.shape[2] is the grid resolution R (Conv3d) or the number of points N (1x1)
+    canon: Callable             # an activation or its gradient, contiguous, as the kernels take it
+    canon_w: Callable           # ... the weight
+    shaped: Callable            # (kernel result, the caller's shape) -> what the caller gets
+    out_shape: Callable         # (B, C, L) -> shape of a (B, C, ...) kernel result
+    wgrad_shape: Callable       # (Co, Ci) -> shape of the weight gradient
+    bias_dims: tuple            # the bias gradient alone: grad_y summed over these
+    amax_seg: Callable          # (backend, L) -> positions per amax segment
+    amax_tiles: Callable        # (B, L, seg) -> segments of one tensor: an amax table has 1 + that many words
+    stats_parts: Callable       # (B, C, L, nsplit) -> arguments of the *_fwd_split_stats_parts query
+    wgrad_f16_ok: Callable      # (backend, x, weight) -> the kind's own bar on the f16x2 backward-weight kernel
+    # a backend's public methods for the kind are <c>_forward, <c>_backward_weight_f16 ... (`method`), except these three
+    amax: str
+    weight_images: str
+    product_split: str
+
+    def entry(self, lib, name):
+        return getattr(lib, f'pvcnn_{self.c}_{name}')
+
+    def method(self, be, name):
+        return getattr(be, f'{self.c}_{name}')
+
+
+def _same(t, shape=None):
+    return t
+
+
+CONV = Product(
+    kind='conv', c='conv3d',
+    canon=_same, canon_w=_same, shaped=_same,
+    out_shape=lambda b, c, r: (b, c, r, r, r), wgrad_shape=lambda co, ci: (co, ci, 3, 3, 3), bias_dims=(0, 2, 3, 4),
+    amax_seg=lambda be, r: r, amax_tiles=lambda b, r, seg: b * r * r,                        # one maximum per z row
+    stats_parts=lambda b, c, r, nsplit: (b, c, r, nsplit),
+    wgrad_f16_ok=lambda be, x, w: True,
+    amax='conv_amax', weight_images='conv_weight_images', product_split='conv3d_igemm_split')
+
+PW = Product(
+    kind='pw', c='pwconv',
+    canon=lambda t: t.view(t.shape[0], t.shape[1], -1), canon_w=lambda w: w.view(w.shape[0], w.shape[1]),
+    shaped=lambda t, shape: t.view(shape),
+    out_shape=lambda b, c, n: (b, c, n), wgrad_shape=lambda co, ci: (co, ci), bias_dims=(0, 2),
+    amax_seg=lambda be, n: be.PW_AMAX_SEG, amax_tiles=lambda b, n, seg: b * ((n + seg - 1) // seg),      # one per point tile
+    stats_parts=lambda b, c, n, nsplit: (b, n),
+    # the f16x2 kernel writes 128 x 128 partial tiles per partition of the points: a loss on small weight matrices
+    wgrad_f16_ok=lambda be, x, w: x.shape[0] * x.shape[2] * w.shape[0] * w.shape[1] >= getattr(be, 'pw_wgrad_f16_min_macs', 0),
+    amax='pw_amax', weight_images='pw_weight_images', product_split='pwconv_gemm_split')
+
+
+def forward(p, be, ctx, given, weight, bias, want_stats, nsplit):
+    """The forward of VoxelConv3d / PointwiseConv on backend `be`.  Both kinds look the amax tag up on `given`, the tensor object
+    the caller handed over (the tag rides on the object: functional/_cache.py), not on its canonical view."""
+    x, w = p.canon(given.contiguous()), p.canon_w(weight.contiguous())
+    ctx.save_for_backward(x, w)
+    ctx.has_bias, ctx.x_shape, ctx.w_shape = bias is not None, given.shape, weight.shape
+    ctx.bias_param = bias                     # (only asked where its gradient should be written: _gradslots.claim)
+    ctx.nsplit = int(nsplit)
+    b = bias.contiguous() if bias is not None else None
+    # f16x2: the input's amax buffer (its power-of-two scales, one per segment) -- left on the tensor by the BatchNorm pass that
+    # wrote it (_cache.tag_amax), else measured here in one read -- is reused by backward-weight
+    ctx.x_amax = None
+    if ctx.nsplit in (1, 2):
+        ctx.x_amax = _cache.amax_of(given, p.amax_seg(be, x.shape[2]))
+        if ctx.x_amax is None and ctx.nsplit == 2:           # (bf16 mode: only backward-weight wants it, and measures it itself)
+            ctx.x_amax = getattr(be, p.amax)(x, want_global=False)      # (every consumer below takes the table)
+    kw = {'amax': ctx.x_amax} if ctx.nsplit == 2 else {}
+    # the pre-split weight images: when the input wants a gradient the backward-data image is made by the SAME launch as the
+    # forward one and kept for backward (the values backward must use are the ones saved now, not a later state of the weight)
+    ctx.w_bwd_image = None
+    if ctx.nsplit and hasattr(be, p.weight_images) and ctx.needs_input_grad[0]:
+        w_image, ctx.w_bwd_image = getattr(be, p.weight_images)(w, ctx.nsplit)
+        run = lambda **k: getattr(be, p.product_split)(x, w_image, b, w.shape[0], ctx.nsplit, amax=ctx.x_amax, **k)
+    elif ctx.nsplit:
+        run = lambda **k: p.method(be, 'forward_split')(x, w, b, ctx.nsplit, **kw, **k)
+    else:
+        run = lambda **k: p.method(be, 'forward')(x, w, b, **k)
+    y_shape = (given.shape[0], w.shape[0], *given.shape[2:])
+    if want_stats:   # second output: BatchNorm partial sums from the epilogue (not differentiable)
+        y, part = run(want_stats=True)
+        ctx.mark_non_differentiable(part)
+        ctx.set_materialize_grads(False)     # no zero tensor for the (non-existent) gradient of `part`
+        return p.shaped(y, y_shape), part
+    return p.shaped(run(), y_shape)
+
+
+def backward(p, be, ctx, received):
+    """The backward of both nodes: (grad_x, grad_weight, grad_bias, None, None)."""
+    x, w = ctx.saved_tensors
+    if received is None:
+        return None, None, None, None, None
+    grad_y = p.canon(received.contiguous())
+    f16 = ctx.nsplit == 2
+    # the f16x2 backward-weight kernel also serves the bf16 (autocast) mode: more accurate than bf16 operands and far faster than the
+    # fp32-MFMA kernel (x_amax / g_amax are None there: the kernel's wrapper takes the global maxima in one read each)
+    wgrad_f16 = (ctx.nsplit in (1, 2) and ctx.needs_input_grad[1] and p.method(be, 'backward_weight_f16_serves')(x)
+                 and p.wgrad_f16_ok(be, x, w))
+    # shared by both products; the BatchNorm backward that produced grad_y left it on the tensor (_cache.tag_amax)
+    g_amax = None
+    if (f16 and (ctx.needs_input_grad[0] or wgrad_f16)) or (ctx.nsplit == 1 and wgrad_f16):
+        g_amax = _cache.amax_of(received, p.amax_seg(be, grad_y.shape[2]))
+        if g_amax is None and f16:
+            g_amax = getattr(be, p.amax)(grad_y, want_global=False)
+    gx = None
+    if ctx.needs_input_grad[0]:
+        if ctx.nsplit and ctx.w_bwd_image is not None:     # the forward product with Ci and Co exchanged, on forward's second image
+            gx = getattr(be, p.product_split)(grad_y, ctx.w_bwd_image, None, w.shape[1], ctx.nsplit, False, g_amax)
+        elif ctx.nsplit:
+            gx = p.method(be, 'backward_data_split')(grad_y, w, ctx.nsplit, **({'amax': g_amax} if f16 else {}))
+        else:
+            gx = p.method(be, 'backward_data')(grad_y, w)
+        gx = p.shaped(gx, ctx.x_shape)
+    want_bias = ctx.has_bias and ctx.needs_input_grad[2]
+    gw = gb = None
+    if ctx.needs_input_grad[1]:
+        # the bias gradient is accumulated by the same kernel from the grad_y tiles it stages anyway
+        dst = _gradslots.destinations(be, w, ctx.bias_param if want_bias else None)   # the parameters' slots in a flat gradient bucket
+        res = (p.method(be, 'backward_weight_f16')(x, grad_y, ctx.x_amax, g_amax, with_bias=want_bias, **dst) if wgrad_f16
+               else p.method(be, 'backward_weight')(x, grad_y, with_bias=want_bias, **dst))
+        gw, gb = res if want_bias else (res, None)
+        gw = p.shaped(gw, ctx.w_shape)
+    elif want_bias:
+        gb = grad_y.sum(dim=p.bias_dims)
+    return gx, gw, gb, None, None

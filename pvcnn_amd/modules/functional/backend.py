@@ -19,6 +19,7 @@ import torch
 
 from ... import _lib
 from . import _cache
+from ._product import CONV, PW
 
 __all__ = ['_backend']
 
@@ -578,15 +579,7 @@ class HipBackend:
     def conv3d_backward_weight(self, x, grad_y, with_bias=False, out_w=None, out_b=None):
         """-> grad_weight, or (grad_weight, grad_bias) when with_bias (the bias sum rides on the same pass)."""
         _f32(x, 'x'); _f32(grad_y, 'grad_y')
-        b, ci, r = x.shape[0], x.shape[1], x.shape[2]
-        co = grad_y.shape[1]
-        gw = self._grad_out(out_w, (co, ci, 3, 3, 3), x.device)
-        gb = self._grad_out(out_b, (co,), x.device) if with_bias else None
-        ws = self._scratch(self.lib.pvcnn_conv3d_bwd_weight_workspace_bytes(b, ci, co, r), x.device)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_conv3d_bwd_weight(_p(x), _p(grad_y), b, ci, co, r, _p(gw), _p(gb) if with_bias else None,
-                                                        _p(ws), ws.numel(), s), 'conv3d_backward_weight')
-        return (gw, gb) if with_bias else gw
+        return self._backward_weight(CONV, x, grad_y, with_bias, out_w, out_b)
 
 
     # ---- the same convolution on the bf16 matrix cores (csrc/conv3d_bf16.hip): nsplit = 3 "bf16x3" (fp32-class accuracy, up to
@@ -646,13 +639,78 @@ class HipBackend:
         _shape(amax.numel() == 1 + tiles, f'amax buffer has {amax.numel()} words, expected 1 or {1 + tiles}')
         return seg
 
-    def _conv_wsplit(self, weight, for_bwd_data, nsplit):
+    # ---- what the Conv3d and the 1x1 convolution share: `p` is the kind's descriptor, CONV or PW (functional/_product.py).  x and
+    # grad_y are (B, C, L ...) with L = the grid resolution R or the number of points N ----
+    def _amax_for(self, p, x, amax=None):
+        """-> (amax buffer of x: the given one, else measured here with its word [0]; the segment length the kernels are told)."""
+        if amax is None:
+            amax = getattr(self, p.amax)(x)
+        seg = p.amax_seg(self, x.shape[2])
+        return amax, self._amax_seg(amax, p.amax_tiles(x.shape[0], x.shape[2], seg), seg)
+
+    def _weight_split(self, p, weight, for_bwd_data, nsplit):
         co, ci = weight.shape[0], weight.shape[1]
-        nbytes = self.lib.pvcnn_conv3d_weight_split_bytes(co, ci, int(for_bwd_data), int(nsplit))
+        nbytes = p.entry(self.lib, 'weight_split_bytes')(co, ci, int(for_bwd_data), int(nsplit))
         wts = torch.empty((nbytes,), dtype=torch.uint8, device=weight.device)
         with _Launch(weight) as s:
-            _lib.check(self.lib.pvcnn_conv3d_weight_split(_p(weight), co, ci, int(for_bwd_data), int(nsplit), _p(wts), s), 'conv3d_weight_split')
+            _lib.check(p.entry(self.lib, 'weight_split')(_p(weight), co, ci, int(for_bwd_data), int(nsplit), _p(wts), s), f'{p.c}_weight_split')
         return wts
+
+    def _weight_images(self, p, weight, nsplit):
+        co, ci = weight.shape[0], weight.shape[1]
+        if int(nsplit) != 2:
+            hit = self._bank().take(p.kind, weight, 1) if int(nsplit) == 1 else None      # plain bf16 (autocast): batched as well
+            if hit is not None:
+                return hit
+            return self._weight_split(p, weight, False, nsplit), self._weight_split(p, weight, True, nsplit)
+        hit = self._bank().take(p.kind, weight)
+        if hit is not None:
+            return hit
+        wf, wb = (torch.empty((p.entry(self.lib, 'weight_split_bytes')(co, ci, for_bwd_data, 2),), dtype=torch.uint8, device=weight.device)
+                  for for_bwd_data in (0, 1))
+        with _Launch(weight) as s:
+            _lib.check(p.entry(self.lib, 'weight_split_pair')(_p(weight), co, ci, _p(wf), _p(wb), s), f'{p.c}_weight_split_pair')
+        return wf, wb
+
+    def _product_split(self, p, x, wts, bias, co, nsplit, want_stats=False, amax=None):
+        """The split kernel's launch alone: x (B, Ci, L ...) and a pre-split weight image -> y (B, co, L ...) [, stats partials]."""
+        b, ci, l = x.shape[0], x.shape[1], x.shape[2]
+        y = torch.empty(p.out_shape(b, co, l), dtype=torch.float32, device=x.device)
+        part = None
+        if want_stats:
+            parts = p.entry(self.lib, 'fwd_split_stats_parts')(*p.stats_parts(b, co, l, int(nsplit)))
+            part = torch.empty((co, parts, 2), dtype=torch.float32, device=x.device)
+        seg = 0
+        if int(nsplit) == 2:
+            amax, seg = self._amax_for(p, x, amax)
+        with _Launch(x) as s:
+            _lib.check(p.entry(self.lib, 'fwd_split')(_p(x), _p(wts), _p(bias) if bias is not None else None, b, ci, co, l, int(nsplit),
+                                                      _p(amax) if amax is not None else None, seg,
+                                                      _p(y), _p(part) if want_stats else None, s), f'{p.c}_forward_split')
+        return (y, part) if want_stats else y
+
+    def _backward_weight(self, p, x, grad_y, with_bias, out_w, out_b, f16_amax=None):
+        """grad_weight [, grad_bias] on the fp32-MFMA kernel, or, with f16_amax = (x_amax, gy_amax) (each an amax buffer or None: one
+        global maximum, measured here), on the f16x2 one.  A buffer with a table is passed with its segment length: the kernel then
+        takes the global maximum from the table (a table-only buffer has no word [0])."""
+        b, ci, l = x.shape[0], x.shape[1], x.shape[2]
+        co = grad_y.shape[1]
+        name, label, scales = 'bwd_weight', f'{p.c}_backward_weight', ()
+        if f16_amax is not None:
+            name, label = name + '_f16', label + '_f16'
+            given = [(t, amax if amax is not None else self.absmax_bits(t)) for t, amax in zip((x, grad_y), f16_amax)]
+            for t, amax in given:
+                scales += (_p(amax), self._amax_for(p, t, amax)[1])
+        gw = self._grad_out(out_w, p.wgrad_shape(co, ci), x.device)
+        gb = self._grad_out(out_b, (co,), x.device) if with_bias else None
+        ws = self._scratch(p.entry(self.lib, name + '_workspace_bytes')(b, ci, co, l), x.device)
+        with _Launch(x) as s:
+            _lib.check(p.entry(self.lib, name)(_p(x), _p(grad_y), *scales, b, ci, co, l, _p(gw), _p(gb) if with_bias else None,
+                                               _p(ws), ws.numel(), s), label)
+        return (gw, gb) if with_bias else gw
+
+    def _conv_wsplit(self, weight, for_bwd_data, nsplit):
+        return self._weight_split(CONV, weight, for_bwd_data, nsplit)
 
     # ---- the f16x2 weight images of a whole model, refreshed by one launch per kind and step ---------------------------------
     has_weight_bank = True
@@ -684,37 +742,11 @@ class HipBackend:
     def conv_weight_images(self, weight, nsplit):
         """(forward image, backward-data image) of a Conv3d weight; f16x2: both from ONE launch (a training step needs both and the
         weights do not change between its forward and its backward)."""
-        co, ci = weight.shape[0], weight.shape[1]
-        if int(nsplit) != 2:
-            hit = self._bank().take('conv', weight, 1) if int(nsplit) == 1 else None      # plain bf16 (autocast): batched as well
-            if hit is not None:
-                return hit
-            return self._conv_wsplit(weight, False, nsplit), self._conv_wsplit(weight, True, nsplit)
-        hit = self._bank().take('conv', weight)
-        if hit is not None:
-            return hit
-        wf = torch.empty((self.lib.pvcnn_conv3d_weight_split_bytes(co, ci, 0, 2),), dtype=torch.uint8, device=weight.device)
-        wb = torch.empty((self.lib.pvcnn_conv3d_weight_split_bytes(co, ci, 1, 2),), dtype=torch.uint8, device=weight.device)
-        with _Launch(weight) as s:
-            _lib.check(self.lib.pvcnn_conv3d_weight_split_pair(_p(weight), co, ci, _p(wf), _p(wb), s), 'conv3d_weight_split_pair')
-        return wf, wb
+        return self._weight_images(CONV, weight, nsplit)
 
     def pw_weight_images(self, weight, nsplit):
         """(forward image, backward-data image) of a 1x1 convolution weight (Co, Ci); f16x2: one launch."""
-        co, ci = weight.shape
-        if int(nsplit) != 2:
-            hit = self._bank().take('pw', weight, 1) if int(nsplit) == 1 else None
-            if hit is not None:
-                return hit
-            return self._pw_wsplit(weight, False, nsplit), self._pw_wsplit(weight, True, nsplit)
-        hit = self._bank().take('pw', weight)
-        if hit is not None:
-            return hit
-        wf = torch.empty((self.lib.pvcnn_pwconv_weight_split_bytes(co, ci, 0, 2),), dtype=torch.uint8, device=weight.device)
-        wb = torch.empty((self.lib.pvcnn_pwconv_weight_split_bytes(co, ci, 1, 2),), dtype=torch.uint8, device=weight.device)
-        with _Launch(weight) as s:
-            _lib.check(self.lib.pvcnn_pwconv_weight_split_pair(_p(weight), co, ci, _p(wf), _p(wb), s), 'pwconv_weight_split_pair')
-        return wf, wb
+        return self._weight_images(PW, weight, nsplit)
 
     def conv3d_forward_split(self, x, weight, bias, nsplit, want_stats=False, amax=None):
         _f32(x, 'x'); _f32(weight, 'weight')
@@ -722,55 +754,30 @@ class HipBackend:
                and x.shape[2] == x.shape[3] == x.shape[4], 'conv3d: x (B,Ci,R,R,R), weight (Co,Ci,3,3,3) expected')
         if bias is not None:
             _f32(bias, 'bias')
-        return self.conv3d_igemm_split(x, self._conv_wsplit(weight, False, nsplit), bias, weight.shape[0], nsplit, want_stats,
-                                       amax if amax is not None else (self.conv_amax(x) if int(nsplit) == 2 else None))
+        return self._product_split(CONV, x, self._weight_split(CONV, weight, False, nsplit), bias, weight.shape[0], nsplit, want_stats, amax)
 
     def conv3d_igemm_split(self, x, wts, bias, co, nsplit, want_stats=False, amax=None):
         """The implicit-GEMM launch alone (pre-split weight image `wts`; f16x2: `amax` = conv_amax(x), or a 1-word absmax_bits(x)
         for the single-scale mode): x (B,Ci,R,R,R) -> y (B,co,R,R,R) [, stats partials]."""
-        b, ci, r = x.shape[0], x.shape[1], x.shape[2]
-        y = torch.empty((b, co, r, r, r), dtype=torch.float32, device=x.device)
-        part = None
-        if want_stats:
-            part = torch.empty((co, self.lib.pvcnn_conv3d_fwd_split_stats_parts(b, co, r, int(nsplit)), 2), dtype=torch.float32, device=x.device)
-        if int(nsplit) == 2 and amax is None:
-            amax = self.conv_amax(x)
-        seg = self._amax_seg(amax, b * r * r, r) if int(nsplit) == 2 else 0
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_conv3d_fwd_split(_p(x), _p(wts), _p(bias) if bias is not None else None, b, ci, co, r, int(nsplit),
-                                                       _p(amax) if amax is not None else None, seg,
-                                                       _p(y), _p(part) if want_stats else None, s), 'conv3d_forward_split')
-        return (y, part) if want_stats else y
+        return self._product_split(CONV, x, wts, bias, co, nsplit, want_stats, amax)
 
     def conv3d_backward_data_split(self, grad_y, weight, nsplit, amax=None):
         _f32(grad_y, 'grad_y'); _f32(weight, 'weight')
-        b, co, r = grad_y.shape[0], grad_y.shape[1], grad_y.shape[2]
-        ci = weight.shape[1]
         # a convolution with Ci and Co exchanged on the flipped weights
-        return self.conv3d_igemm_split(grad_y, self._conv_wsplit(weight, True, nsplit), None, ci, nsplit, False,
-                                       amax if amax is not None else (self.conv_amax(grad_y) if int(nsplit) == 2 else None))
+        return self._product_split(CONV, grad_y, self._weight_split(CONV, weight, True, nsplit), None, weight.shape[1], nsplit, False, amax)
 
     # ---- backward-weight in f16x2 (csrc/conv3d_wgrad_f16.hip): R = 8, 12, 16 and 32; other grids stay on the fp32-MFMA kernel ----
     def conv3d_backward_weight_f16_serves(self, x):
         return x.dim() == 5 and x.shape[2] in (8, 12, 16, 32)
 
     def conv3d_backward_weight_f16(self, x, grad_y, x_amax=None, gy_amax=None, with_bias=False, out_w=None, out_b=None):
-        """grad_w (Co,Ci,3,3,3) [, grad_bias]: x (B,Ci,R,R,R), grad_y (B,Co,R,R,R); *_amax = amax buffers of the two tensors (word [0],
-        the global maximum, is what this kernel scales by)."""
+        """grad_w (Co,Ci,3,3,3) [, grad_bias]: x (B,Ci,R,R,R), grad_y (B,Co,R,R,R); *_amax = amax buffers of the two tensors.  The
+        kernel scales by each tensor's global maximum: the one word of a 1-word buffer, else the maximum over the table (ABI v12:
+        word [0] of a table-only buffer is uninitialised and never read)."""
         _f32(x, 'x'); _f32(grad_y, 'grad_y')
-        b, ci, r = x.shape[0], x.shape[1], x.shape[2]
-        co = grad_y.shape[1]
-        _shape(self.conv3d_backward_weight_f16_serves(x) and tuple(grad_y.shape) == (b, co, r, r, r), 'conv3d_backward_weight_f16: R must be 8, 12, 16 or 32')
-        x_amax = x_amax if x_amax is not None else self.absmax_bits(x)
-        gy_amax = gy_amax if gy_amax is not None else self.absmax_bits(grad_y)
-        gw = self._grad_out(out_w, (co, ci, 3, 3, 3), x.device)
-        gb = self._grad_out(out_b, (co,), x.device) if with_bias else None
-        ws = self._scratch(self.lib.pvcnn_conv3d_bwd_weight_f16_workspace_bytes(b, ci, co, r), x.device)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_conv3d_bwd_weight_f16(_p(x), _p(grad_y), _p(x_amax), self._amax_seg(x_amax, b * r * r, r), _p(gy_amax),
-                                                            self._amax_seg(gy_amax, b * r * r, r), b, ci, co, r, _p(gw),
-                                                            _p(gb) if with_bias else None, _p(ws), ws.numel(), s), 'conv3d_backward_weight_f16')
-        return (gw, gb) if with_bias else gw
+        _shape(self.conv3d_backward_weight_f16_serves(x) and tuple(grad_y.shape) == CONV.out_shape(x.shape[0], grad_y.shape[1], x.shape[2]),
+               'conv3d_backward_weight_f16: R must be 8, 12, 16 or 32')
+        return self._backward_weight(CONV, x, grad_y, with_bias, out_w, out_b, (x_amax, gy_amax))
 
     # ---- SharedMLP 1x1 convolutions as channel-major MFMA GEMMs (csrc/pointwise.hip) --------------------
     has_pwconv = True
@@ -822,53 +829,28 @@ class HipBackend:
     pw_wgrad_f16_min_macs = 1 << 32
 
     def _pw_wsplit(self, weight, for_bwd_data, nsplit):
-        co, ci = weight.shape
-        nbytes = self.lib.pvcnn_pwconv_weight_split_bytes(co, ci, int(for_bwd_data), int(nsplit))
-        wts = torch.empty((nbytes,), dtype=torch.uint8, device=weight.device)
-        with _Launch(weight) as s:
-            _lib.check(self.lib.pvcnn_pwconv_weight_split(_p(weight), co, ci, int(for_bwd_data), int(nsplit), _p(wts), s), 'pwconv_weight_split')
-        return wts
+        return self._weight_split(PW, weight, for_bwd_data, nsplit)
 
     def pwconv_gemm_split(self, x, wts, bias, m, nsplit, want_stats=False, amax=None):
         """The GEMM launch alone: x (B,K,N), pre-split weight image (f16x2: amax = pw_amax(x), or a 1-word absmax_bits(x) for the
         single-scale mode) -> y (B,m,N) [, stats partials]."""
-        b, k, n = x.shape
-        y = torch.empty((b, m, n), dtype=torch.float32, device=x.device)
-        part = None
-        if want_stats:
-            part = torch.empty((m, self.lib.pvcnn_pwconv_fwd_split_stats_parts(b, n), 2), dtype=torch.float32, device=x.device)
-        if int(nsplit) == 2 and amax is None:
-            amax = self.pw_amax(x)
-        seg = self._amax_seg(amax, b * ((n + self.PW_AMAX_SEG - 1) // self.PW_AMAX_SEG), self.PW_AMAX_SEG) if int(nsplit) == 2 else 0
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_pwconv_fwd_split(_p(x), _p(wts), _p(bias) if bias is not None else None, b, k, m, n, int(nsplit),
-                                                       _p(amax) if amax is not None else None, seg,
-                                                       _p(y), _p(part) if want_stats else None, s), 'pwconv_forward_split')
-        return (y, part) if want_stats else y
+        return self._product_split(PW, x, wts, bias, m, nsplit, want_stats, amax)
 
     def pwconv_forward_split(self, x, weight, bias, nsplit, want_stats=False, amax=None):
         _f32(x, 'x'); _f32(weight, 'weight')
         _shape(x.dim() == 3 and weight.dim() == 2 and weight.shape[1] == x.shape[1], 'pwconv: x (B,Ci,N), weight (Co,Ci) expected')
         if bias is not None:
             _f32(bias, 'bias')
-        return self.pwconv_gemm_split(x, self._pw_wsplit(weight, False, nsplit), bias, weight.shape[0], nsplit, want_stats, amax)
+        return self._product_split(PW, x, self._weight_split(PW, weight, False, nsplit), bias, weight.shape[0], nsplit, want_stats, amax)
 
     def pwconv_backward_data_split(self, grad_y, weight, nsplit, amax=None):
         _f32(grad_y, 'grad_y'); _f32(weight, 'weight')
-        return self.pwconv_gemm_split(grad_y, self._pw_wsplit(weight, True, nsplit), None, weight.shape[1], nsplit, False, amax)
+        return self._product_split(PW, grad_y, self._weight_split(PW, weight, True, nsplit), None, weight.shape[1], nsplit, False, amax)
 
     def pwconv_backward_weight(self, x, grad_y, with_bias=False, out_w=None, out_b=None):
         """-> grad_weight (Co,Ci), or (grad_weight, grad_bias) when with_bias."""
         _f32(x, 'x'); _f32(grad_y, 'grad_y')
-        b, ci, n = x.shape
-        co = grad_y.shape[1]
-        gw = self._grad_out(out_w, (co, ci), x.device)
-        gb = self._grad_out(out_b, (co,), x.device) if with_bias else None
-        ws = self._scratch(self.lib.pvcnn_pwconv_bwd_weight_workspace_bytes(b, ci, co, n), x.device)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_pwconv_bwd_weight(_p(x), _p(grad_y), b, ci, co, n, _p(gw), _p(gb) if with_bias else None,
-                                                        _p(ws), ws.numel(), s), 'pwconv_backward_weight')
-        return (gw, gb) if with_bias else gw
+        return self._backward_weight(PW, x, grad_y, with_bias, out_w, out_b)
 
     def pwconv_backward_weight_f16_serves(self, x):
         return x.dim() == 3 and x.shape[2] % 4 == 0
@@ -876,20 +858,9 @@ class HipBackend:
     def pwconv_backward_weight_f16(self, x, grad_y, x_amax=None, gy_amax=None, with_bias=False, out_w=None, out_b=None):
         """f16x2 on the fp16 matrix cores (csrc/pointwise_wgrad_f16.hip): -> grad_weight (Co,Ci) [, grad_bias]."""
         _f32(x, 'x'); _f32(grad_y, 'grad_y')
-        b, ci, n = x.shape
-        co = grad_y.shape[1]
-        _shape(self.pwconv_backward_weight_f16_serves(x) and tuple(grad_y.shape) == (b, co, n), 'pwconv_backward_weight_f16: N must be a multiple of 4')
-        x_amax = x_amax if x_amax is not None else self.absmax_bits(x)
-        gy_amax = gy_amax if gy_amax is not None else self.absmax_bits(grad_y)
-        gw = self._grad_out(out_w, (co, ci), x.device)
-        gb = self._grad_out(out_b, (co,), x.device) if with_bias else None
-        ws = self._scratch(self.lib.pvcnn_pwconv_bwd_weight_f16_workspace_bytes(b, ci, co, n), x.device)
-        with _Launch(x) as s:
-            tiles = b * ((n + self.PW_AMAX_SEG - 1) // self.PW_AMAX_SEG)
-            _lib.check(self.lib.pvcnn_pwconv_bwd_weight_f16(_p(x), _p(grad_y), _p(x_amax), self._amax_seg(x_amax, tiles, self.PW_AMAX_SEG), _p(gy_amax),
-                                                            self._amax_seg(gy_amax, tiles, self.PW_AMAX_SEG), b, ci, co, n, _p(gw),
-                                                            _p(gb) if with_bias else None, _p(ws), ws.numel(), s), 'pwconv_backward_weight_f16')
-        return (gw, gb) if with_bias else gw
+        _shape(self.pwconv_backward_weight_f16_serves(x) and tuple(grad_y.shape) == PW.out_shape(x.shape[0], grad_y.shape[1], x.shape[2]),
+               'pwconv_backward_weight_f16: N must be a multiple of 4')
+        return self._backward_weight(PW, x, grad_y, with_bias, out_w, out_b, (x_amax, gy_amax))
 
     # ---- BatchNorm + ReLU/LeakyReLU in two passes each way (csrc/bnact.hip) ---------------------------
     has_bnact = True
@@ -1631,6 +1602,10 @@ class _WeightBank:
     (Co, Ci)); `wanted` = the keys a forward pass asked for (take() misses note them), so a refresh computes what is used and nothing
     else; the device tables are rebuilt when that set changes (the warm-up steps), not in steady state."""
 
+    _PRODUCTS = {CONV.kind: CONV, PW.kind: PW}
+    # lib.pvcnn_<conv3d|pwconv>_weight_split_pair_<entry|batch><suffix>: the f16x2 pairs (nsplit 2), the plain-bf16 pairs of autocast (1)
+    _PAIR_SUFFIX = {2: '', 1: '_bf16'}
+
     def __init__(self, be):
         import weakref
         self.be, self._weakref = be, weakref
@@ -1684,7 +1659,7 @@ class _WeightBank:
     def _rebuild(self):
         lib = self.be.lib
         # (kind, nsplit): nsplit 2 = the f16x2 pairs, 1 = the plain-bf16 pairs of the autocast mode
-        live, by_kind = {}, {('conv', 2): [], ('pw', 2): [], ('conv', 1): [], ('pw', 1): []}
+        live, by_kind = {}, {(kind, nsplit): [] for nsplit in self._PAIR_SUFFIX for kind in self._PRODUCTS}
         for ref in self.params:
             p = ref()
             if p is None or not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
@@ -1697,7 +1672,7 @@ class _WeightBank:
                 e = self.entries.get(key)
                 if e is None or e['param']() is not p:
                     co, ci = key[2]
-                    nbytes = lib.pvcnn_conv3d_weight_split_bytes if kind == 'conv' else lib.pvcnn_pwconv_weight_split_bytes
+                    nbytes = self._PRODUCTS[kind].entry(lib, 'weight_split_bytes')
                     e = {'param': ref, 'armed': False, 'version': -1, 'epoch': -1,
                          'wf': torch.empty((nbytes(co, ci, 0, nsplit),), dtype=torch.uint8, device=p.device),
                          'wb': torch.empty((nbytes(co, ci, 1, nsplit),), dtype=torch.uint8, device=p.device)}
@@ -1707,8 +1682,7 @@ class _WeightBank:
         for (kind, nsplit), items in by_kind.items():
             if not items:
                 continue
-            fill = {('conv', 2): lib.pvcnn_conv3d_weight_split_pair_entry, ('pw', 2): lib.pvcnn_pwconv_weight_split_pair_entry,
-                    ('conv', 1): lib.pvcnn_conv3d_weight_split_pair_entry_bf16, ('pw', 1): lib.pvcnn_pwconv_weight_split_pair_entry_bf16}[(kind, nsplit)]
+            fill = self._PRODUCTS[kind].entry(lib, 'weight_split_pair_entry' + self._PAIR_SUFFIX[nsplit])
             host = torch.zeros((len(items), 10), dtype=torch.int64)
             rows = 0
             for i, (key, p, e) in enumerate(items):
@@ -1730,10 +1704,8 @@ class _WeightBank:
             self._rebuild()
         capturing = torch.cuda.is_current_stream_capturing()
         lib = self.be.lib
-        launches = {('conv', 2): lib.pvcnn_conv3d_weight_split_pair_batch, ('pw', 2): lib.pvcnn_pwconv_weight_split_pair_batch,
-                    ('conv', 1): lib.pvcnn_conv3d_weight_split_pair_batch_bf16, ('pw', 1): lib.pvcnn_pwconv_weight_split_pair_batch_bf16}
-        for kind, (table, n, rows, keys, dev) in self.tables.items():
-            launch = launches[kind]
+        for (kind, nsplit), (table, n, rows, keys, dev) in self.tables.items():
+            launch = self._PRODUCTS[kind].entry(lib, 'weight_split_pair_batch' + self._PAIR_SUFFIX[nsplit])
             with _Launch(table) as s:
                 _lib.check(launch(_p(table), n, rows, s), 'weight_split_pair_batch')
             if capturing:                               # the captured launch walks this table and writes every entry's buffers on replay
