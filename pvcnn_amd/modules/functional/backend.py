@@ -103,6 +103,19 @@ class _Launch:
         return self.guard.__exit__(*exc)
 
 
+def _run(fn, label, ref, *args):
+    """One native call on `ref`'s device and torch's current stream: a tensor among `args` goes as its device pointer (_p: an empty
+    one as NULL), None as NULL, everything else as it is; the stream goes last; a non-zero return code raises, naming `label`."""
+    conv = [_p(a) if a is None or isinstance(a, torch.Tensor) else a for a in args]
+    with _Launch(ref) as s:
+        _lib.check(fn(*conv, s), label)
+
+
+def _mean_rstd(c, device):
+    """The uninitialised (mean, rstd) pair of a BatchNorm over c channels."""
+    return torch.empty((c,), dtype=torch.float32, device=device), torch.empty((c,), dtype=torch.float32, device=device)
+
+
 class HipBackend:
     name = 'hip-gfx950'
 
@@ -154,8 +167,7 @@ class HipBackend:
         b, c, n = features.shape
         m = indices.shape[1]
         out = torch.empty((b, c, m), dtype=torch.float32, device=features.device)
-        with _Launch(features) as s:
-            _lib.check(self.lib.pvcnn_gather_fwd(_p(features), _p(indices), b, c, n, m, _p(out), s), 'gather_features_forward')
+        _run(self.lib.pvcnn_gather_fwd, 'gather_features_forward', features, features, indices, b, c, n, m, out)
         return out
 
     def gather_features_backward(self, grad_y, indices, n):
@@ -165,9 +177,7 @@ class HipBackend:
         b, c, m = grad_y.shape
         grad_x = torch.empty((b, c, int(n)), dtype=torch.float32, device=grad_y.device)
         ws = self._scratch(self.lib.pvcnn_gather_bwd_workspace_bytes(b, c, int(n), m), grad_y.device)
-        with _Launch(grad_y) as s:
-            _lib.check(self.lib.pvcnn_gather_bwd(_p(grad_y), _p(indices), b, c, int(n), m, _p(grad_x), _p(ws), ws.numel(), s),
-                       'gather_features_backward')
+        _run(self.lib.pvcnn_gather_bwd, 'gather_features_backward', grad_y, grad_y, indices, b, c, int(n), m, grad_x, ws, ws.numel())
         return grad_x
 
     # ---- sampling.cpp:43-58 -----------------------------------------------------------------
@@ -180,8 +190,7 @@ class HipBackend:
         distances = None
         if n > 16384:   # PVCNN_FPS_MAX_RESIDENT_POINTS: larger clouds need the global scratch
             distances = torch.empty((b, n), dtype=torch.float32, device=coords.device)
-        with _Launch(coords) as s:
-            _lib.check(self.lib.pvcnn_fps(_p(coords), b, n, m, _p(distances), _p(indices), s), 'furthest_point_sampling')
+        _run(self.lib.pvcnn_fps, 'furthest_point_sampling', coords, coords, b, n, m, distances, indices)
         return indices
 
     # ---- the index selection of logits_mask (modules/functional/sampling.py:69-82) on the device ----------------
@@ -201,9 +210,8 @@ class HipBackend:
             _dev(seed, 'seed')
             _shape(seed.dtype == torch.int64 and seed.numel() >= 2 and seed.is_contiguous(), 'mask_select: seed = 2 x int64 on the device')
         selected = torch.empty((b, m), dtype=torch.int32, device=mask.device)
-        with _Launch(mask) as s:
-            _lib.check(self.lib.pvcnn_mask_select(_p(mask.view(torch.uint8)), b, n, m, _p(choices) if choices is not None else None,
-                                                  _p(seed) if choices is None else None, _p(selected), None, s), 'mask_select')
+        _run(self.lib.pvcnn_mask_select, 'mask_select', mask, mask.view(torch.uint8), b, n, m, choices, seed if choices is None else None,
+             selected, None)
         return selected
 
     # ---- batches assembled on the device (csrc/batch.hip; pvcnn_amd/data.py checks shapes and owns the tensors) ----------------
@@ -212,19 +220,12 @@ class HipBackend:
     def batch_launch(self, entry, ref, *args):
         """One pvcnn_batch_* launch on `ref`'s device and torch's current stream.  Tensors among `args` are passed as device
         pointers (None as NULL) and must live on that device, contiguous; ints go through as they are."""
-        conv = []
         for a in args:
             if isinstance(a, torch.Tensor):
                 _dev(a, entry)
                 _shape(a.is_contiguous() and a.device == ref.device, f'{entry}: contiguous tensors on one device expected')
-                conv.append(ctypes.c_void_p(a.data_ptr()))
-            elif a is None:
-                conv.append(ctypes.c_void_p(None))
-            else:
-                conv.append(int(a))
         _dev(ref, entry)
-        with _Launch(ref) as s:
-            _lib.check(getattr(self.lib, 'pvcnn_' + entry)(*conv, s), entry)
+        _run(getattr(self.lib, 'pvcnn_' + entry), entry, ref, *(a if a is None or isinstance(a, torch.Tensor) else int(a) for a in args))
 
     # ---- ball_query.cpp:6-30 ----------------------------------------------------------------
     def ball_query(self, centers_coords, points_coords, radius, num_neighbors):
@@ -236,8 +237,7 @@ class HipBackend:
         n = points_coords.shape[2]
         u = int(num_neighbors)
         out = torch.empty((b, m, u), dtype=torch.int32, device=centers_coords.device)
-        with _Launch(centers_coords) as s:
-            _lib.check(self.lib.pvcnn_ball_query(_p(centers_coords), _p(points_coords), b, n, m, float(radius), u, _p(out), s), 'ball_query')
+        _run(self.lib.pvcnn_ball_query, 'ball_query', centers_coords, centers_coords, points_coords, b, n, m, float(radius), u, out)
         return out
 
     # ---- grouping.cpp:6-44 ------------------------------------------------------------------
@@ -248,8 +248,7 @@ class HipBackend:
         b, c, n = features.shape
         _, m, u = indices.shape
         out = torch.empty((b, c, m, u), dtype=torch.float32, device=features.device)
-        with _Launch(features) as s:
-            _lib.check(self.lib.pvcnn_grouping_fwd(_p(features), _p(indices), b, c, n, m, u, _p(out), s), 'grouping_forward')
+        _run(self.lib.pvcnn_grouping_fwd, 'grouping_forward', features, features, indices, b, c, n, m, u, out)
         return out
 
     def grouping_backward(self, grad_y, indices, n):
@@ -259,9 +258,7 @@ class HipBackend:
         b, c, m, u = grad_y.shape
         grad_x = torch.empty((b, c, int(n)), dtype=torch.float32, device=grad_y.device)
         ws = self._scratch(self.lib.pvcnn_grouping_bwd_workspace_bytes(b, c, int(n), m, u), grad_y.device)
-        with _Launch(grad_y) as s:
-            _lib.check(self.lib.pvcnn_grouping_bwd(_p(grad_y), _p(indices), b, c, int(n), m, u, _p(grad_x), _p(ws), ws.numel(), s),
-                       'grouping_backward')
+        _run(self.lib.pvcnn_grouping_bwd, 'grouping_backward', grad_y, grad_y, indices, b, c, int(n), m, u, grad_x, ws, ws.numel())
         return grad_x
 
     # ---- neighbor_interpolate.cpp:6-65 ------------------------------------------------------
@@ -278,10 +275,8 @@ class HipBackend:
         indices = torch.empty((b, 3, n), dtype=torch.int32, device=dev)
         weights = torch.empty((b, 3, n), dtype=torch.float32, device=dev)
         out = torch.empty((b, c, n), dtype=torch.float32, device=dev)
-        with _Launch(points_coords) as s:
-            _lib.check(self.lib.pvcnn_three_nn_interp_fwd(_p(points_coords), _p(centers_coords), _p(centers_features),
-                                                          b, c, m, n, _p(indices), _p(weights), _p(out), s),
-                       'three_nearest_neighbors_interpolate_forward')
+        _run(self.lib.pvcnn_three_nn_interp_fwd, 'three_nearest_neighbors_interpolate_forward', points_coords,
+             points_coords, centers_coords, centers_features, b, c, m, n, indices, weights, out)
         return [out, indices, weights]
 
     def three_nearest_neighbors_interpolate_backward(self, grad_y, indices, weights, m):
@@ -292,10 +287,8 @@ class HipBackend:
         b, c, n = grad_y.shape
         grad_x = torch.empty((b, c, int(m)), dtype=torch.float32, device=grad_y.device)
         ws = self._scratch(self.lib.pvcnn_three_nn_interp_bwd_workspace_bytes(b, c, n, int(m)), grad_y.device)
-        with _Launch(grad_y) as s:
-            _lib.check(self.lib.pvcnn_three_nn_interp_bwd(_p(grad_y), _p(indices), _p(weights), b, c, n, int(m), _p(grad_x),
-                                                          _p(ws), ws.numel(), s),
-                       'three_nearest_neighbors_interpolate_backward')
+        _run(self.lib.pvcnn_three_nn_interp_bwd, 'three_nearest_neighbors_interpolate_backward', grad_y,
+             grad_y, indices, weights, b, c, n, int(m), grad_x, ws, ws.numel())
         return grad_x
 
     # the two scatter entries of the 12-callable seam keep their plan on the tensor they were called with (False: the one-shot C entries,
@@ -318,11 +311,8 @@ class HipBackend:
             wgts = torch.empty((b, 8, n), dtype=torch.float32, device=dev)
         else:   # 1-element dummies, like trilinear_devox.cpp:45-53
             inds, wgts = _dummies(dev)
-        with _Launch(features) as s:
-            _lib.check(self.lib.pvcnn_trilinear_devox_fwd(_p(coords), _p(features), b, c, n, r, int(bool(is_training)),
-                                                          _p(inds) if is_training else None,
-                                                          _p(wgts) if is_training else None, _p(outs), s),
-                       'trilinear_devoxelize_forward')
+        _run(self.lib.pvcnn_trilinear_devox_fwd, 'trilinear_devoxelize_forward', features, coords, features, b, c, n, r,
+             int(bool(is_training)), inds if is_training else None, wgts if is_training else None, outs)
         return [outs, inds, wgts]
 
     def trilinear_devoxelize_backward(self, grad_y, indices, weights, r):
@@ -343,10 +333,8 @@ class HipBackend:
                 return self.trilinear_devoxelize_backward_apply(grad_y, plan, r)
         grad_x = torch.empty((b, c, r * r * r), dtype=torch.float32, device=grad_y.device)
         ws = self._scratch(self.lib.pvcnn_trilinear_devox_bwd_workspace_bytes(b, c, n, r), grad_y.device)
-        with _Launch(grad_y) as s:
-            _lib.check(self.lib.pvcnn_trilinear_devox_bwd_strided(_p(grad_y), gy_bstride, _p(indices), _p(weights), b, c, n, r,
-                                                                  _p(grad_x), _p(ws), ws.numel(), s),
-                       'trilinear_devoxelize_backward')
+        _run(self.lib.pvcnn_trilinear_devox_bwd_strided, 'trilinear_devoxelize_backward', grad_y,
+             grad_y, gy_bstride, indices, weights, b, c, n, r, grad_x, ws, ws.numel())
         return grad_x
 
     # ---- modules/voxelization.py:16-25 ---------------------------------------------------------
@@ -359,9 +347,7 @@ class HipBackend:
         b, _, n = coords.shape
         norm = torch.empty_like(coords)
         vox = torch.empty((b, 3, n), dtype=torch.int32, device=coords.device)
-        with _Launch(coords) as s:
-            _lib.check(self.lib.pvcnn_voxel_coords(_p(coords), b, n, int(resolution), int(bool(normalize)), float(eps),
-                                                   _p(norm), _p(vox), s), 'voxel_coords')
+        _run(self.lib.pvcnn_voxel_coords, 'voxel_coords', coords, coords, b, n, int(resolution), int(bool(normalize)), float(eps), norm, vox)
         return norm, vox
 
     def voxel_coords_tail(self, coords, mean, radius, resolution, eps):
@@ -378,9 +364,8 @@ class HipBackend:
             _shape(radius.numel() == b, 'voxel_coords: radius (B) expected')
         norm = torch.empty((b, 3, n), dtype=torch.float32, device=coords.device)
         vox = torch.empty((b, 3, n), dtype=torch.int32, device=coords.device)
-        with _Launch(coords) as s:
-            _lib.check(self.lib.pvcnn_voxel_coords_tail(_p(coords), cstride, _p(mean), _p(radius) if radius is not None else None,
-                                                        b, n, int(resolution), float(eps), _p(norm), _p(vox), s), 'voxel_coords_tail')
+        _run(self.lib.pvcnn_voxel_coords_tail, 'voxel_coords_tail', coords, coords, cstride, mean, radius, b, n, int(resolution), float(eps),
+             norm, vox)
         return norm, vox
 
     # ---- vox.cpp:17-76 ----------------------------------------------------------------------
@@ -408,9 +393,7 @@ class HipBackend:
         ind = torch.empty((b, n), dtype=torch.int32, device=dev)
         cnt = torch.empty((b, s3), dtype=torch.int32, device=dev)
         ws = self._scratch(self.lib.pvcnn_avg_voxelize_fwd_workspace_bytes(b, c, n, r), dev)
-        with _Launch(features) as s:
-            _lib.check(self.lib.pvcnn_avg_voxelize_fwd(_p(features), _p(coords), b, c, n, r, _p(out), _p(ind), _p(cnt),
-                                                       _p(ws), ws.numel(), s), 'avg_voxelize_forward')
+        _run(self.lib.pvcnn_avg_voxelize_fwd, 'avg_voxelize_forward', features, features, coords, b, c, n, r, out, ind, cnt, ws, ws.numel())
         return [out, ind, cnt]
 
     def _stamped_voxel_plan(self, coords, r):
@@ -425,11 +408,8 @@ class HipBackend:
         b, c, s3 = grad_y.shape
         n = indices.shape[1]
         grad_x = torch.empty((b, c, n), dtype=torch.float32, device=grad_y.device)
-        with _Launch(grad_y) as s:
-            _lib.check(self.lib.pvcnn_avg_voxelize_bwd(_p(grad_y), _p(indices), _p(cnt), b, c, n, s3, _p(grad_x), s),
-                       'avg_voxelize_backward')
+        _run(self.lib.pvcnn_avg_voxelize_bwd, 'avg_voxelize_backward', grad_y, grad_y, indices, cnt, b, c, n, s3, grad_x)
         return grad_x
-
 
     # ---- scatter plans (include/pvcnn_hip.h "scatter plans"): one counting sort per (coords, R), applied by every layer ----
     has_scatter_plans = True
@@ -437,6 +417,15 @@ class HipBackend:
     class VoxelPlan:
         """avg_voxelize's plan for one (voxel coordinates, R): ind (B,N), cnt (B,R^3) and the opaque sort plan."""
         __slots__ = ('ind', 'cnt', 'plan', 'r', 'n', 'b')
+
+    def _voxel_plan(self, b, n, r, nbytes, dev):
+        """An empty VoxelPlan for (B, N, R) whose opaque plan takes nbytes."""
+        vp = self.VoxelPlan()
+        vp.r, vp.n, vp.b = r, n, b
+        vp.ind = torch.empty((b, n), dtype=torch.int32, device=dev)
+        vp.cnt = torch.empty((b, r * r * r), dtype=torch.int32, device=dev)
+        vp.plan = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        return vp
 
     def avg_voxelize_plan(self, coords, resolution):
         """coords (B,3,N) int32 -> VoxelPlan, or None when the grid is too large for a plan (one-shot path then)."""
@@ -447,16 +436,10 @@ class HipBackend:
         nbytes = self.lib.pvcnn_avg_voxelize_plan_bytes(b, n, r)
         if nbytes == 0:
             return None
-        dev = coords.device
-        vp = self.VoxelPlan()
-        vp.r, vp.n, vp.b = r, n, b
-        vp.ind = torch.empty((b, n), dtype=torch.int32, device=dev)
-        vp.cnt = torch.empty((b, r * r * r), dtype=torch.int32, device=dev)
-        vp.plan = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-        scratch = self._scratch(self.lib.pvcnn_avg_voxelize_plan_scratch_bytes(b, n, r), dev)
-        with _Launch(coords) as s:
-            _lib.check(self.lib.pvcnn_avg_voxelize_plan(_p(coords), b, n, r, _p(vp.ind), _p(vp.cnt), _p(vp.plan), vp.plan.numel(),
-                                                        _p(scratch), scratch.numel(), s), 'avg_voxelize_plan')
+        vp = self._voxel_plan(b, n, r, nbytes, coords.device)
+        scratch = self._scratch(self.lib.pvcnn_avg_voxelize_plan_scratch_bytes(b, n, r), coords.device)
+        _run(self.lib.pvcnn_avg_voxelize_plan, 'avg_voxelize_plan', coords, coords, b, n, r, vp.ind, vp.cnt, vp.plan, vp.plan.numel(),
+             scratch, scratch.numel())
         return vp
 
     # PVCNN_PAIR_PLANS=0 (read once per process): the two plans of a PVConv geometry from their own chains (A/B; the pair is the default)
@@ -475,16 +458,11 @@ class HipBackend:
         if vbytes == 0 or dbytes == 0 or n == 0:
             return None
         dev = vox_coords.device
-        vp = self.VoxelPlan()
-        vp.r, vp.n, vp.b = r, n, b
-        vp.ind = torch.empty((b, n), dtype=torch.int32, device=dev)
-        vp.cnt = torch.empty((b, r * r * r), dtype=torch.int32, device=dev)
-        vp.plan = torch.empty((vbytes,), dtype=torch.uint8, device=dev)
+        vp = self._voxel_plan(b, n, r, vbytes, dev)
         dplan = torch.empty((dbytes,), dtype=torch.uint8, device=dev)
         scratch = self._scratch(self.lib.pvcnn_pvconv_plans_scratch_bytes(b, n, r), dev)
-        with _Launch(vox_coords) as s:
-            _lib.check(self.lib.pvcnn_pvconv_plans(_p(vox_coords), _p(norm_coords), b, n, r, _p(vp.ind), _p(vp.cnt), _p(vp.plan), vp.plan.numel(),
-                                                   _p(dplan), dplan.numel(), _p(scratch), scratch.numel(), s), 'pvconv_plans')
+        _run(self.lib.pvcnn_pvconv_plans, 'pvconv_plans', vox_coords, vox_coords, norm_coords, b, n, r, vp.ind, vp.cnt, vp.plan, vp.plan.numel(),
+             dplan, dplan.numel(), scratch, scratch.numel())
         return vp, dplan
 
     def avg_voxelize_apply(self, features, vp):
@@ -493,9 +471,7 @@ class HipBackend:
         _shape(features.dim() == 3 and features.shape[0] == vp.b and features.shape[2] == vp.n, 'avg_voxelize: features do not match the plan')
         b, c, n = features.shape
         out = torch.empty((b, c, vp.r ** 3), dtype=torch.float32, device=features.device)
-        with _Launch(features) as s:
-            _lib.check(self.lib.pvcnn_avg_voxelize_apply(_p(features), _p(vp.plan), vp.plan.numel(), b, c, n, vp.r, _p(out), s),
-                       'avg_voxelize_apply')
+        _run(self.lib.pvcnn_avg_voxelize_apply, 'avg_voxelize_apply', features, features, vp.plan, vp.plan.numel(), b, c, n, vp.r, out)
         return out
 
     def trilinear_devoxelize_backward_plan(self, indices, weights, r):
@@ -509,9 +485,8 @@ class HipBackend:
             return None
         plan = torch.empty((nbytes,), dtype=torch.uint8, device=indices.device)
         scratch = self._scratch(self.lib.pvcnn_trilinear_devox_bwd_plan_scratch_bytes(b, n, r), indices.device)
-        with _Launch(indices) as s:
-            _lib.check(self.lib.pvcnn_trilinear_devox_bwd_plan(_p(indices), _p(weights), b, n, r, _p(plan), plan.numel(),
-                                                               _p(scratch), scratch.numel(), s), 'trilinear_devoxelize_backward_plan')
+        _run(self.lib.pvcnn_trilinear_devox_bwd_plan, 'trilinear_devoxelize_backward_plan', indices, indices, weights, b, n, r,
+             plan, plan.numel(), scratch, scratch.numel())
         return plan
 
     def trilinear_devoxelize_backward_apply(self, grad_y, plan, r):
@@ -519,9 +494,8 @@ class HipBackend:
         b, c, n = grad_y.shape
         r = int(r)
         grad_x = torch.empty((b, c, r * r * r), dtype=torch.float32, device=grad_y.device)
-        with _Launch(grad_y) as s:
-            _lib.check(self.lib.pvcnn_trilinear_devox_bwd_apply(_p(grad_y), gy_bstride, _p(plan), plan.numel(), b, c, n, r,
-                                                                _p(grad_x), s), 'trilinear_devoxelize_backward_apply')
+        _run(self.lib.pvcnn_trilinear_devox_bwd_apply, 'trilinear_devoxelize_backward_apply', grad_y, grad_y, gy_bstride, plan, plan.numel(),
+             b, c, n, r, grad_x)
         return grad_x
 
     # ---- voxel_layers Conv3d (k=3, stride 1, pad 1): modules/pvconv.py:20-27 (cuDNN in the reference) ----
@@ -530,8 +504,7 @@ class HipBackend:
     def _conv_wt(self, weight, for_bwd_data):
         co, ci = weight.shape[0], weight.shape[1]
         wt = torch.empty((ci * 27 * co,), dtype=torch.float32, device=weight.device)
-        with _Launch(weight) as s:
-            _lib.check(self.lib.pvcnn_conv3d_weight_transform(_p(weight), co, ci, int(for_bwd_data), _p(wt), s), 'conv3d_weight_transform')
+        _run(self.lib.pvcnn_conv3d_weight_transform, 'conv3d_weight_transform', weight, weight, co, ci, int(for_bwd_data), wt)
         return wt
 
     def conv3d_forward(self, x, weight, bias, want_stats=False):
@@ -546,12 +519,9 @@ class HipBackend:
         y = torch.empty((b, co, r, r, r), dtype=torch.float32, device=x.device)
         if want_stats:   # per-workgroup (sum, sum of squares) partials for the BatchNorm that follows
             part = torch.empty((co, self.lib.pvcnn_conv3d_fwd_stats_parts(b, co, r), 2), dtype=torch.float32, device=x.device)
-            with _Launch(x) as s:
-                _lib.check(self.lib.pvcnn_conv3d_fwd_stats(_p(x), _p(wt), _p(bias) if bias is not None else None, b, ci, co, r,
-                                                           _p(y), _p(part), s), 'conv3d_forward')
+            _run(self.lib.pvcnn_conv3d_fwd_stats, 'conv3d_forward', x, x, wt, bias, b, ci, co, r, y, part)
             return y, part
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_conv3d_fwd(_p(x), _p(wt), _p(bias) if bias is not None else None, b, ci, co, r, _p(y), s), 'conv3d_forward')
+        _run(self.lib.pvcnn_conv3d_fwd, 'conv3d_forward', x, x, wt, bias, b, ci, co, r, y)
         return y
 
     def conv3d_backward_data(self, grad_y, weight):
@@ -560,8 +530,8 @@ class HipBackend:
         ci = weight.shape[1]
         wt = self._conv_wt(weight, True)
         gx = torch.empty((b, ci, r, r, r), dtype=torch.float32, device=grad_y.device)
-        with _Launch(grad_y) as s:   # a convolution with Ci and Co exchanged on the flipped weights
-            _lib.check(self.lib.pvcnn_conv3d_fwd(_p(grad_y), _p(wt), None, b, co, ci, r, _p(gx), s), 'conv3d_backward_data')
+        # a convolution with Ci and Co exchanged on the flipped weights
+        _run(self.lib.pvcnn_conv3d_fwd, 'conv3d_backward_data', grad_y, grad_y, wt, None, b, co, ci, r, gx)
         return gx
 
     # the backward-weight / BatchNorm-backward entries take `out_w` / `out_b`: where to write the two parameter gradients (contiguous
@@ -581,7 +551,6 @@ class HipBackend:
         _f32(x, 'x'); _f32(grad_y, 'grad_y')
         return self._backward_weight(CONV, x, grad_y, with_bias, out_w, out_b)
 
-
     # ---- the same convolution on the bf16 matrix cores (csrc/conv3d_bf16.hip): nsplit = 3 "bf16x3" (fp32-class accuracy, up to
     # 2.7x the fp32-MFMA rate) or nsplit = 1 (plain bf16 operands: the autocast / BASELINE configs[4] path) ----
     has_conv3d_split = True
@@ -596,8 +565,7 @@ class HipBackend:
         """One uint32 on the device: the bit pattern of max |x| (a 1-word amax buffer: the scalar scale of the f16x2 kernels)."""
         _f32(x, 'x')
         out = torch.empty((1,), dtype=torch.int32, device=x.device)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_absmax_bits(_p(x), x.numel(), _p(out), s), 'absmax_bits')
+        _run(self.lib.pvcnn_absmax_bits, 'absmax_bits', x, x, x.numel(), out)
         return out
 
     # "amax buffers" (include/pvcnn_hip.h): [0] = bits of max |x| over the tensor, [1 + t] = bits of the maximum over all channels of
@@ -618,9 +586,7 @@ class HipBackend:
         out = torch.empty((self.lib.pvcnn_absmax_tiles_count(b, n, seg),), dtype=torch.int32, device=x.device)
         ticket = self._tickets(1, x.device)
         want_global = want_global or self.amax_global
-        tk = (_p(ticket) if ticket is not None else None) if want_global else self._TABLE_ONLY
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_absmax_tiles(_p(x), b, c, n, seg, _p(out), tk, s), 'absmax_tiles')
+        _run(self.lib.pvcnn_absmax_tiles, 'absmax_tiles', x, x, b, c, n, seg, out, ticket if want_global else self._TABLE_ONLY)
         return out
 
     def conv_amax(self, x, want_global=True):
@@ -652,8 +618,7 @@ class HipBackend:
         co, ci = weight.shape[0], weight.shape[1]
         nbytes = p.entry(self.lib, 'weight_split_bytes')(co, ci, int(for_bwd_data), int(nsplit))
         wts = torch.empty((nbytes,), dtype=torch.uint8, device=weight.device)
-        with _Launch(weight) as s:
-            _lib.check(p.entry(self.lib, 'weight_split')(_p(weight), co, ci, int(for_bwd_data), int(nsplit), _p(wts), s), f'{p.c}_weight_split')
+        _run(p.entry(self.lib, 'weight_split'), f'{p.c}_weight_split', weight, weight, co, ci, int(for_bwd_data), int(nsplit), wts)
         return wts
 
     def _weight_images(self, p, weight, nsplit):
@@ -668,8 +633,7 @@ class HipBackend:
             return hit
         wf, wb = (torch.empty((p.entry(self.lib, 'weight_split_bytes')(co, ci, for_bwd_data, 2),), dtype=torch.uint8, device=weight.device)
                   for for_bwd_data in (0, 1))
-        with _Launch(weight) as s:
-            _lib.check(p.entry(self.lib, 'weight_split_pair')(_p(weight), co, ci, _p(wf), _p(wb), s), f'{p.c}_weight_split_pair')
+        _run(p.entry(self.lib, 'weight_split_pair'), f'{p.c}_weight_split_pair', weight, weight, co, ci, wf, wb)
         return wf, wb
 
     def _product_split(self, p, x, wts, bias, co, nsplit, want_stats=False, amax=None):
@@ -683,10 +647,7 @@ class HipBackend:
         seg = 0
         if int(nsplit) == 2:
             amax, seg = self._amax_for(p, x, amax)
-        with _Launch(x) as s:
-            _lib.check(p.entry(self.lib, 'fwd_split')(_p(x), _p(wts), _p(bias) if bias is not None else None, b, ci, co, l, int(nsplit),
-                                                      _p(amax) if amax is not None else None, seg,
-                                                      _p(y), _p(part) if want_stats else None, s), f'{p.c}_forward_split')
+        _run(p.entry(self.lib, 'fwd_split'), f'{p.c}_forward_split', x, x, wts, bias, b, ci, co, l, int(nsplit), amax, seg, y, part)
         return (y, part) if want_stats else y
 
     def _backward_weight(self, p, x, grad_y, with_bias, out_w, out_b, f16_amax=None):
@@ -700,13 +661,11 @@ class HipBackend:
             name, label = name + '_f16', label + '_f16'
             given = [(t, amax if amax is not None else self.absmax_bits(t)) for t, amax in zip((x, grad_y), f16_amax)]
             for t, amax in given:
-                scales += (_p(amax), self._amax_for(p, t, amax)[1])
+                scales += (amax, self._amax_for(p, t, amax)[1])
         gw = self._grad_out(out_w, p.wgrad_shape(co, ci), x.device)
         gb = self._grad_out(out_b, (co,), x.device) if with_bias else None
         ws = self._scratch(p.entry(self.lib, name + '_workspace_bytes')(b, ci, co, l), x.device)
-        with _Launch(x) as s:
-            _lib.check(p.entry(self.lib, name)(_p(x), _p(grad_y), *scales, b, ci, co, l, _p(gw), _p(gb) if with_bias else None,
-                                               _p(ws), ws.numel(), s), label)
+        _run(p.entry(self.lib, name), label, x, x, grad_y, *scales, b, ci, co, l, gw, gb, ws, ws.numel())
         return (gw, gb) if with_bias else gw
 
     def _conv_wsplit(self, weight, for_bwd_data, nsplit):
@@ -796,13 +755,11 @@ class HipBackend:
         part = None
         if want_stats:
             part = torch.empty((co, self.lib.pvcnn_pwconv_fwd_stats_parts(b, n), 2), dtype=torch.float32, device=x.device)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_pwconv_transpose(_p(weight), co, ci, _p(wt), s), 'pwconv_transpose')
-            if want_stats:
-                _lib.check(self.lib.pvcnn_pwconv_fwd_stats(_p(x), _p(wt), k32, _p(bias) if bias is not None else None, b, ci, co, n,
-                                                           _p(y), _p(part), s), 'pwconv_forward')
-            else:
-                _lib.check(self.lib.pvcnn_pwconv_fwd(_p(x), _p(wt), k32, _p(bias) if bias is not None else None, b, ci, co, n, _p(y), s), 'pwconv_forward')
+        _run(self.lib.pvcnn_pwconv_transpose, 'pwconv_transpose', x, weight, co, ci, wt)
+        if want_stats:
+            _run(self.lib.pvcnn_pwconv_fwd_stats, 'pwconv_forward', x, x, wt, k32, bias, b, ci, co, n, y, part)
+        else:
+            _run(self.lib.pvcnn_pwconv_fwd, 'pwconv_forward', x, x, wt, k32, bias, b, ci, co, n, y)
         return (y, part) if want_stats else y
 
     def pwconv_backward_data(self, grad_y, weight):
@@ -811,8 +768,7 @@ class HipBackend:
         b, co, n = grad_y.shape
         ci = weight.shape[1]
         gx = torch.empty((b, ci, n), dtype=torch.float32, device=grad_y.device)
-        with _Launch(grad_y) as s:
-            _lib.check(self.lib.pvcnn_pwconv_fwd(_p(grad_y), _p(weight), co, None, b, co, ci, n, _p(gx), s), 'pwconv_backward_data')
+        _run(self.lib.pvcnn_pwconv_fwd, 'pwconv_backward_data', grad_y, grad_y, weight, co, None, b, co, ci, n, gx)
         return gx
 
     # ---- the same GEMMs on the bf16 matrix cores (csrc/pointwise_bf16.hip), nsplit = 3 (bf16x3) or 1 (bf16) ----
@@ -872,8 +828,7 @@ class HipBackend:
     def dropout_keep_mask(self, seed, p, numel):
         """keep(e), e = 0 .. numel - 1, of the dropout fused into bnact_forward / bnact_backward (drop=(seed, p)) -> bool tensor (tests)."""
         keep = torch.empty((int(numel),), dtype=torch.uint8, device=seed.device)
-        with _Launch(seed) as s:
-            _lib.check(self.lib.pvcnn_dropout_keep_mask(_p(seed), float(p), int(numel), _p(keep), s), 'dropout_keep_mask')
+        _run(self.lib.pvcnn_dropout_keep_mask, 'dropout_keep_mask', seed, seed, float(p), int(numel), keep)
         return keep.bool()
 
     def bnact_forward(self, x, gamma, beta, running_mean, running_var, training, momentum, eps, slope, stats=None, amax_seg=0,
@@ -893,25 +848,19 @@ class HipBackend:
             mean, rstd = stats
             training = False                    # the kernel entry's "statistics are given" mode
         elif training:
-            mean = torch.empty((c,), dtype=torch.float32, device=dev)
-            rstd = torch.empty((c,), dtype=torch.float32, device=dev)
+            mean, rstd = _mean_rstd(c, dev)
         else:
             mean = running_mean.clone()          # saved for backward: must not alias the live buffer
             rstd = torch.rsqrt(running_var + eps)
         ws = self._scratch(self.lib.pvcnn_bnact_workspace_bytes(b, c, s3), dev)
-        nul = ctypes.c_void_p(None)
         amax_seg = int(amax_seg)
         armed = y_amax is not None
         if amax_seg > 0 and not armed:
             y_amax = self.amax_buffer(b, s3, amax_seg, dev)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_bnact_fwd(_p(x), _p(gamma) if gamma is not None else nul, _p(beta) if beta is not None else nul,
-                                                _p(running_mean) if (training and running_mean is not None) else nul,
-                                                _p(running_var) if (training and running_var is not None) else nul,
-                                                b, c, s3, float(eps), float(momentum), float(slope), int(bool(training)),
-                                                _p(mean), _p(rstd), _p(y), _p(y_amax) if amax_seg > 0 else nul, amax_seg, int(armed),
-                                                _p(ws), ws.numel(), _p(drop[0]) if drop else nul, float(drop[1]) if drop else 0.0, s),
-                       'bnact_forward')
+        _run(self.lib.pvcnn_bnact_fwd, 'bnact_forward', x, x, gamma, beta, running_mean if training else None,
+             running_var if training else None, b, c, s3, float(eps), float(momentum), float(slope), int(bool(training)), mean, rstd, y,
+             y_amax if amax_seg > 0 else None, amax_seg, int(armed), ws, ws.numel(), drop[0] if drop else None,
+             float(drop[1]) if drop else 0.0)
         return (y, mean, rstd, y_amax) if amax_seg > 0 else (y, mean, rstd)
 
     has_bnact_rowmax = True
@@ -944,12 +893,9 @@ class HipBackend:
         ybs = int(y.stride(0)) if b > 1 else c * s3
         winners = torch.empty((b, c), dtype=torch.int64, device=x.device)
         values = torch.empty((b, c), dtype=torch.float32, device=x.device)
-        nul = ctypes.c_void_p(None)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_bnact_apply_rowmax(_p(x), _p(gamma) if gamma is not None else nul, _p(beta) if beta is not None else nul,
-                                                         _p(mean), _p(rstd), b, c, s3, float(slope), _p(y), ybs, _p(y_amax), int(amax_seg),
-                                                         _p(row_keys), s), 'bnact_apply_rowmax')
-            _lib.check(self.lib.pvcnn_row_keys_decode(_p(row_keys), _p(y), b * c, s3, _p(winners), _p(values), c, ybs, s), 'row_keys_decode')
+        _run(self.lib.pvcnn_bnact_apply_rowmax, 'bnact_apply_rowmax', x, x, gamma, beta, mean, rstd, b, c, s3, float(slope), y, ybs, y_amax,
+             int(amax_seg), row_keys)
+        _run(self.lib.pvcnn_row_keys_decode, 'row_keys_decode', x, row_keys, y, b * c, s3, winners, values, c, ybs)
         return y, winners, values
 
     has_devox_bnact = True
@@ -964,34 +910,19 @@ class HipBackend:
         apply pass that follows, which fills it by atomic maxima: bnact_forward(..., y_amax=zero_word)).  counter: the module's int64 num_batches_tracked,
         incremented by the same launch."""
         c, nparts = part.shape[0], part.shape[1]
-        dev = part.device
-        mean = torch.empty((c,), dtype=torch.float32, device=dev)
-        rstd = torch.empty((c,), dtype=torch.float32, device=dev)
-        nul = ctypes.c_void_p(None)
-        with _Launch(part) as s:
-            _lib.check(self.lib.pvcnn_bn_finalize(_p(part), c, nparts, float(count), float(eps), float(momentum),
-                                                  _p(shift) if shift is not None else nul,
-                                                  _p(running_mean) if running_mean is not None else nul,
-                                                  _p(running_var) if running_var is not None else nul, _p(mean), _p(rstd),
-                                                  _p(zero_word) if zero_word is not None else nul,
-                                                  zero_word.numel() if zero_word is not None else 0,
-                                                  _p(counter) if counter is not None else nul, s),
-                       'bn_finalize')
+        mean, rstd = _mean_rstd(c, part.device)
+        _run(self.lib.pvcnn_bn_finalize, 'bn_finalize', part, part, c, nparts, float(count), float(eps), float(momentum), shift,
+             running_mean, running_var, mean, rstd, zero_word, zero_word.numel() if zero_word is not None else 0, counter)
         return mean, rstd
 
     def bn_stats(self, x, running_mean, running_var, momentum, eps):
         """Training-mode statistics of x (B,C,S): -> (mean, rstd); running stats updated in place (may be None)."""
         _f32(x, 'x')
         b, c, s3 = x.shape
-        dev = x.device
-        mean = torch.empty((c,), dtype=torch.float32, device=dev)
-        rstd = torch.empty((c,), dtype=torch.float32, device=dev)
-        ws = self._scratch(self.lib.pvcnn_bnact_workspace_bytes(b, c, s3), dev)
-        nul = ctypes.c_void_p(None)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_bn_stats(_p(x), _p(running_mean) if running_mean is not None else nul,
-                                               _p(running_var) if running_var is not None else nul, b, c, s3, float(eps),
-                                               float(momentum), _p(mean), _p(rstd), _p(ws), ws.numel(), s), 'bn_stats')
+        mean, rstd = _mean_rstd(c, x.device)
+        ws = self._scratch(self.lib.pvcnn_bnact_workspace_bytes(b, c, s3), x.device)
+        _run(self.lib.pvcnn_bn_stats, 'bn_stats', x, x, running_mean, running_var, b, c, s3, float(eps), float(momentum), mean, rstd,
+             ws, ws.numel())
         return mean, rstd
 
     def trilinear_devoxelize_bnact_forward(self, r, is_training, coords, features, gamma, beta, mean, rstd, slope, addend=None,
@@ -1018,14 +949,9 @@ class HipBackend:
             wgts = torch.empty((b, 8, n), dtype=torch.float32, device=dev)
         else:
             inds, wgts = _dummies(dev)
-        nul = ctypes.c_void_p(None)
-        with _Launch(features) as s:
-            _lib.check(self.lib.pvcnn_trilinear_devox_bnact_fwd(
-                _p(coords), _p(features), _p(gamma) if gamma is not None else nul, _p(beta) if beta is not None else nul,
-                _p(mean), _p(rstd), float(slope), b, c, n, r, int(bool(is_training)),
-                _p(inds) if is_training else None, _p(wgts) if is_training else None,
-                _p(addend) if addend is not None else None, _p(se_scale) if se_scale is not None else None, _p(outs), s),
-                'trilinear_devoxelize_bnact_forward')
+        _run(self.lib.pvcnn_trilinear_devox_bnact_fwd, 'trilinear_devoxelize_bnact_forward', features, coords, features, gamma, beta,
+             mean, rstd, float(slope), b, c, n, r, int(bool(is_training)), inds if is_training else None,
+             wgts if is_training else None, addend, se_scale, outs)
         return [outs, inds, wgts]
 
     # ---- torch.cat(features, dim=1) of the classifier input + the amax buffer of its output in one pass (csrc/bnact.hip) ----
@@ -1065,12 +991,9 @@ class HipBackend:
             pre[i] = table.data_ptr()
         amax = self.amax_buffer(b, n, self.PW_AMAX_SEG, out.device) if want_amax else None
         ticket = self._tickets(1, out.device) if want_amax else None
-        with _Launch(out) as s:
-            _lib.check(self.lib.pvcnn_concat_points((ctypes.c_void_p * k)(*ptrs), (ctypes.c_long * k)(*bstr), (ctypes.c_int * k)(*chans),
-                                                    (ctypes.c_int * k)(*pstr), (ctypes.c_void_p * k)(*pre) if in_place else None, k, b, n,
-                                                    _p(out), _p(amax) if want_amax else None,
-                                                    (_p(ticket) if ticket is not None else None) if want_global or self.amax_global or not want_amax else self._TABLE_ONLY,
-                                                    s), 'concat_points')
+        _run(self.lib.pvcnn_concat_points, 'concat_points', out, (ctypes.c_void_p * k)(*ptrs), (ctypes.c_long * k)(*bstr),
+             (ctypes.c_int * k)(*chans), (ctypes.c_int * k)(*pstr), (ctypes.c_void_p * k)(*pre) if in_place else None, k, b, n, out, amax,
+             ticket if want_global or self.amax_global or not want_amax else self._TABLE_ONLY)
         return out, amax
 
     # ---- the two halves of bnact_backward on their own (PVConv's SE tail puts the excitation's backward between them) ----
@@ -1092,13 +1015,9 @@ class HipBackend:
         dev = x.device
         z = torch.empty((rows, cout), dtype=torch.float32, device=dev)
         y = torch.empty((rows, cout), dtype=torch.float32, device=dev)
-        mean = torch.empty((cout,), dtype=torch.float32, device=dev)
-        rstd = torch.empty((cout,), dtype=torch.float32, device=dev)
-        opt = lambda t: _p(t) if t is not None else ctypes.c_void_p(None)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_dense_bn_relu_fwd(_p(x), _p(weight), opt(bias), opt(gamma), opt(beta), opt(running_mean), opt(running_var),
-                                                        opt(counter), rows, cin, cout, float(eps), float(momentum), _p(z), _p(y), _p(mean),
-                                                        _p(rstd), s), 'dense_bn_relu_forward')
+        mean, rstd = _mean_rstd(cout, dev)
+        _run(self.lib.pvcnn_dense_bn_relu_fwd, 'dense_bn_relu_forward', x, x, weight, bias, gamma, beta, running_mean, running_var, counter,
+             rows, cin, cout, float(eps), float(momentum), z, y, mean, rstd)
         return y, z, mean, rstd
 
     def dense_bn_relu_backward(self, x, grad_y, z, mean, rstd, gamma, beta, out_w=None, out_b=None, out_gamma=None, out_beta=None):
@@ -1113,10 +1032,8 @@ class HipBackend:
         gb = self._grad_out(out_b, (cout,), dev)
         gg = self._grad_out(out_gamma, (cout,), dev)
         gbeta = self._grad_out(out_beta, (cout,), dev)
-        opt = lambda t: _p(t) if t is not None else ctypes.c_void_p(None)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_dense_bn_relu_bwd(_p(x), _p(grad_y), _p(z), _p(mean), _p(rstd), opt(gamma), opt(beta), rows, cin, cout,
-                                                        _p(gz), _p(gw), _p(gb), _p(gg), _p(gbeta), s), 'dense_bn_relu_backward')
+        _run(self.lib.pvcnn_dense_bn_relu_bwd, 'dense_bn_relu_backward', x, x, grad_y, z, mean, rstd, gamma, beta, rows, cin, cout,
+             gz, gw, gb, gg, gbeta)
         return gz, gw, gb, gg, gbeta
 
     # ---- max over the neighbours of a centre (modules/pointnet.py:85) ------------------------------------------------
@@ -1132,8 +1049,7 @@ class HipBackend:
         rows = x.numel() // k
         out = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
         winners = torch.empty(x.shape[:-1], dtype=torch.uint8, device=x.device)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_neighbor_max_fwd(_p(x), rows, k, _p(out), _p(winners), s), 'neighbor_max_forward')
+        _run(self.lib.pvcnn_neighbor_max_fwd, 'neighbor_max_forward', x, x, rows, k, out, winners)
         return out, winners
 
     def neighbor_max_backward(self, grad_out, winners, k):
@@ -1141,8 +1057,7 @@ class HipBackend:
         _f32(grad_out, 'grad_out')
         _shape(grad_out.shape == winners.shape and winners.dtype == torch.uint8 and winners.is_contiguous(), 'neighbor_max: winners (...) uint8 expected')
         gx = torch.empty(tuple(grad_out.shape) + (int(k),), dtype=torch.float32, device=grad_out.device)
-        with _Launch(grad_out) as s:
-            _lib.check(self.lib.pvcnn_neighbor_max_bwd(_p(grad_out), _p(winners), grad_out.numel(), int(k), _p(gx), s), 'neighbor_max_backward')
+        _run(self.lib.pvcnn_neighbor_max_bwd, 'neighbor_max_backward', grad_out, grad_out, winners, grad_out.numel(), int(k), gx)
         return gx
 
     def row_argmax(self, x, with_values=False):
@@ -1152,8 +1067,7 @@ class HipBackend:
         _shape(k % 4 == 0 and k > 0, 'row_argmax: the last dimension must be a multiple of 4')
         winners = torch.empty(x.shape[:-1], dtype=torch.int64, device=x.device)
         values = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device) if with_values else None
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_row_argmax(_p(x), x.numel() // k, k, _p(winners), _p(values), s), 'row_argmax')
+        _run(self.lib.pvcnn_row_argmax, 'row_argmax', x, x, x.numel() // k, k, winners, values)
         return (winners, values) if with_values else winners
 
     has_frustum_loss = True
@@ -1175,12 +1089,9 @@ class HipBackend:
                and heading_bin_id.is_contiguous() and size_template_id.is_contiguous(), 'frustum_box_loss: shapes of modules/frustum.py:57-75 expected')
         loss = torch.empty((), dtype=torch.float32, device=center.device)
         grads = torch.empty((self.lib.pvcnn_frustum_box_loss_grad_floats(b, nh, ns),), dtype=torch.float32, device=center.device)
-        with _Launch(center) as s:
-            _lib.check(self.lib.pvcnn_frustum_box_loss(_p(center), _p(center_reg), _p(heading_scores), _p(size_scores), _p(hrn), _p(srn), _p(hr),
-                                                       _p(sr), _p(heading_bin_id), _p(size_template_id), _p(heading_residual),
-                                                       _p(size_residual), _p(center_t), _p(templates), _p(bin_centers), b, nh, ns,
-                                                       float(bin_width), float(w_heading), float(w_size), float(w_corners), _p(loss),
-                                                       _p(grads), s), 'frustum_box_loss')
+        _run(self.lib.pvcnn_frustum_box_loss, 'frustum_box_loss', center, *outs, heading_bin_id, size_template_id, heading_residual,
+             size_residual, center_t, templates, bin_centers, b, nh, ns, float(bin_width), float(w_heading), float(w_size),
+             float(w_corners), loss, grads)
         return loss, grads
 
     has_se_excite = True
@@ -1194,11 +1105,8 @@ class HipBackend:
         dev = part.device
         a_sum, ax_sum, squeezed, excite = (torch.empty((b, c), dtype=torch.float32, device=dev) for _ in range(4))
         hidden = torch.empty((b, h), dtype=torch.float32, device=dev)
-        nul = ctypes.c_void_p(None)
-        with _Launch(part) as s:
-            _lib.check(self.lib.pvcnn_se_excite_fwd(_p(part), slices, _p(gamma) if gamma is not None else nul, _p(beta) if beta is not None else nul,
-                                                    _p(w1), _p(w2), b, c, h, 1.0 / float(s3), _p(a_sum), _p(ax_sum), _p(squeezed), _p(hidden),
-                                                    _p(excite), s), 'se_excite_fwd')
+        _run(self.lib.pvcnn_se_excite_fwd, 'se_excite_fwd', part, part, slices, gamma, beta, w1, w2, b, c, h, 1.0 / float(s3),
+             a_sum, ax_sum, squeezed, hidden, excite)
         return a_sum, ax_sum, squeezed, hidden, excite
 
     def se_excite_backward(self, part, a_sum, ax_sum, gamma, beta, squeezed, hidden, excite, w1, w2, s3):
@@ -1213,12 +1121,8 @@ class HipBackend:
         sum_beta = torch.empty((c,), dtype=torch.float32, device=dev)
         sum_gamma = torch.empty((c,), dtype=torch.float32, device=dev)
         ws = torch.empty((b * (3 * c + h),), dtype=torch.float32, device=dev)
-        nul = ctypes.c_void_p(None)
-        with _Launch(part) as s:
-            _lib.check(self.lib.pvcnn_se_excite_bwd(_p(part), slices, _p(a_sum), _p(ax_sum), _p(gamma) if gamma is not None else nul,
-                                                    _p(beta) if beta is not None else nul, _p(squeezed), _p(hidden), _p(excite), _p(w1), _p(w2),
-                                                    b, c, h, 1.0 / float(s3), _p(g_w1), _p(g_w2), _p(g_mean), _p(sum_beta), _p(sum_gamma),
-                                                    _p(ws), s), 'se_excite_bwd')
+        _run(self.lib.pvcnn_se_excite_bwd, 'se_excite_bwd', part, part, slices, a_sum, ax_sum, gamma, beta, squeezed, hidden, excite, w1, w2,
+             b, c, h, 1.0 / float(s3), g_w1, g_w2, g_mean, sum_beta, sum_gamma, ws)
         return g_w1, g_w2, g_mean, sum_beta, sum_gamma
 
     def bnact_partial_sums_raw(self, x, grad_y, gamma, beta, mean, rstd, slope):
@@ -1228,11 +1132,8 @@ class HipBackend:
         gy_bstride = _f32_rows(grad_y, 'grad_y') if grad_y is not None else c * s3
         slices = self.lib.pvcnn_bnact_slices(s3)
         part = torch.empty((c, b, slices, 2), dtype=torch.float32, device=x.device)
-        nul = ctypes.c_void_p(None)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_bnact_partial_sums(_p(x), _p(grad_y) if grad_y is not None else nul, gy_bstride,
-                                                         _p(gamma) if gamma is not None else nul, _p(beta) if beta is not None else nul,
-                                                         _p(mean), _p(rstd), b, c, s3, float(slope), _p(part), s), 'bnact_partial_sums')
+        _run(self.lib.pvcnn_bnact_partial_sums, 'bnact_partial_sums', x, x, grad_y, gy_bstride, gamma, beta, mean, rstd, b, c, s3,
+             float(slope), part)
         return part
 
     def bnact_partial_sums(self, x, grad_y, gamma, beta, mean, rstd, slope):
@@ -1253,14 +1154,8 @@ class HipBackend:
                 _shape(tuple(t.shape) == (b, c), f'{name} (B,C) expected')
         gx = torch.empty_like(x)
         amax = self.amax_buffer(b, s3, amax_seg, x.device)
-        nul = ctypes.c_void_p(None)
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_bnact_bwd_apply(_p(x), _p(grad_y), gy_bstride, _p(gamma) if gamma is not None else nul,
-                                                      _p(beta) if beta is not None else nul, _p(mean), _p(rstd),
-                                                      _p(sum_gamma) if sum_gamma is not None else nul, _p(sum_beta) if sum_beta is not None else nul,
-                                                      _p(bc_mul) if bc_mul is not None else nul, _p(bc_add) if bc_add is not None else nul,
-                                                      b, c, s3, float(slope), int(bool(training)), _p(gx), _p(amax), int(amax_seg), s),
-                       'bnact_backward_apply')
+        _run(self.lib.pvcnn_bnact_bwd_apply, 'bnact_backward_apply', x, x, grad_y, gy_bstride, gamma, beta, mean, rstd, sum_gamma, sum_beta,
+             bc_mul, bc_add, b, c, s3, float(slope), int(bool(training)), gx, amax, int(amax_seg))
         return gx, amax
 
     def bnact_backward(self, x, grad_y, gamma, beta, mean, rstd, slope, training, amax_seg=0, drop=None, out_w=None, out_b=None):
@@ -1274,19 +1169,13 @@ class HipBackend:
         gg = self._grad_out(out_w, (c,), dev)
         gb = self._grad_out(out_b, (c,), dev)
         ws = self._scratch(self.lib.pvcnn_bnact_workspace_bytes(b, c, s3), dev)
-        nul = ctypes.c_void_p(None)
         amax_seg = int(amax_seg)
         gx_amax = self.amax_buffer(b, s3, amax_seg, dev) if amax_seg > 0 else None
         tickets = self._tickets(c, dev)                   # one word per channel: the reduce pass finalises its own sums
-        with _Launch(x) as s:
-            _lib.check(self.lib.pvcnn_bnact_bwd_strided(_p(x), _p(grad_y), gy_bstride, _p(gamma) if gamma is not None else nul,
-                                                        _p(beta) if beta is not None else nul, _p(mean), _p(rstd), b, c, s3, float(slope),
-                                                        int(bool(training)), _p(gx), _p(gg), _p(gb),
-                                                        _p(gx_amax) if amax_seg > 0 else nul, amax_seg, _p(ws), ws.numel(),
-                                                        _p(drop[0]) if drop else nul, float(drop[1]) if drop else 0.0,
-                                                        _p(tickets) if tickets is not None else nul, s), 'bnact_backward')
+        _run(self.lib.pvcnn_bnact_bwd_strided, 'bnact_backward', x, x, grad_y, gy_bstride, gamma, beta, mean, rstd, b, c, s3, float(slope),
+             int(bool(training)), gx, gg, gb, gx_amax, amax_seg, ws, ws.numel(), drop[0] if drop else None,
+             float(drop[1]) if drop else 0.0, tickets)
         return (gx, gg, gb, gx_amax) if amax_seg > 0 else (gx, gg, gb)
-
 
     # ---- evaluation (csrc/evaluate.hip, ABI v13): evaluate/{s3dis,shapenet}/eval.py and meters/{s3dis,shapenet}.py on the device --------
     def eval_tile(self, src, shuffled, num_points, channels, strides, src_points):
@@ -1301,8 +1190,7 @@ class HipBackend:
         _shape(min(bs, ps, cs) >= 0 and (b == 0 or (b - 1) * bs + (int(src_points) - 1) * ps + (c - 1) * cs < src.numel()),
                'eval_tile: strides reach beyond src')
         out = torch.empty((b * (v // np_), c, np_), dtype=torch.float32, device=src.device)
-        with _Launch(src) as s:
-            _lib.check(self.lib.pvcnn_eval_tile(_p(src), bs, ps, cs, int(src_points), _p(shuffled), b, v, np_, c, _p(out), s), 'eval_tile')
+        _run(self.lib.pvcnn_eval_tile, 'eval_tile', src, src, bs, ps, cs, int(src_points), shuffled, b, v, np_, c, out)
         return out
 
     def vote_confidence(self, logits, class_range=None):
@@ -1323,8 +1211,7 @@ class HipBackend:
             _shape(0 <= c0 < c1 <= c, 'vote_confidence: class range must satisfy 0 <= c0 < c1 <= C')
         conf = torch.empty((b, n), dtype=torch.float32, device=logits.device)
         pred = torch.empty((b, n), dtype=torch.int32, device=logits.device)
-        with _Launch(logits) as s:
-            _lib.check(self.lib.pvcnn_vote_confidence(_p(logits), b, c, n, c0, c1, _p(table), _p(conf), _p(pred), s), 'vote_confidence')
+        _run(self.lib.pvcnn_vote_confidence, 'vote_confidence', logits, logits, b, c, n, c0, c1, table, conf, pred)
         return conf, pred
 
     def vote_merge(self, conf, pred, shuffled, scene_conf, scene_pred, keys, mapping=None):
@@ -1345,9 +1232,8 @@ class HipBackend:
             _shape(mapping.dtype == torch.int64 and mapping.is_contiguous() and mapping.dim() == 2 and mapping.shape[0] >= b,
                    'vote_merge: mapping (>= B, M) contiguous int64 expected')
             map_stride = mapping.shape[1]
-        with _Launch(conf) as s:
-            _lib.check(self.lib.pvcnn_vote_merge(_p(conf), _p(pred), _p(shuffled), _p(mapping), map_stride, b, v, p, _p(scene_conf),
-                                                 _p(scene_pred), _p(keys), keys.numel() * 8, s), 'vote_merge')
+        _run(self.lib.pvcnn_vote_merge, 'vote_merge', conf, conf, pred, shuffled, mapping, map_stride, b, v, p, scene_conf, scene_pred,
+             keys, keys.numel() * 8)
 
     def seg_counts(self, gt, pred, num_classes, counts=None, wrap_negative=True):
         """counts (3, C) int64 += [seen; positive; correct] of (gt, pred) (int64, P each); a new zeroed buffer when counts is None."""
@@ -1359,8 +1245,7 @@ class HipBackend:
         if counts is None:
             counts = torch.zeros((3, c), dtype=torch.int64, device=gt.device)
         _shape(counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == 3 * c, 'seg_counts: counts (3,C) int64')
-        with _Launch(gt) as s:
-            _lib.check(self.lib.pvcnn_seg_counts(_p(gt), _p(pred), gt.numel(), c, int(bool(wrap_negative)), _p(counts), s), 'seg_counts')
+        _run(self.lib.pvcnn_seg_counts, 'seg_counts', gt, gt, pred, gt.numel(), c, int(bool(wrap_negative)), counts)
         return counts
 
     def seg_meter_update(self, logits, targets, counts=None, part_ranges=None, max_parts=0, rows=None, row_cursor=None):
@@ -1370,22 +1255,20 @@ class HipBackend:
         _shape(logits.dim() == 3 and targets.dtype == torch.int64 and targets.is_contiguous()
                and tuple(targets.shape) == (logits.shape[0], logits.shape[2]), 'seg_meter_update: logits (B,C,N), targets (B,N) int64')
         b, c, n = logits.shape
-        with _Launch(logits) as s:
-            if part_ranges is None:
-                _shape(counts is not None and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == 3 * c + 2,
-                       'seg_meter_update: counts (3C+2) int64 expected')
-                rc = self.lib.pvcnn_seg_meter_update(_p(logits), _p(targets), b, c, n, None, 0, 0, _p(counts), None, None, 0, s)
-            else:
-                _i32(part_ranges, 'part_ranges')
-                _shape(part_ranges.dim() == 2 and part_ranges.shape[1] == 2, 'seg_meter_update: part_ranges (K,2) int32 expected')
-                _i32(rows, 'rows')
-                _shape(rows.dim() == 3 and rows.shape[1:] == (int(max_parts) + 1, 2), 'seg_meter_update: rows (capacity, max_parts+1, 2)')
-                if row_cursor is not None:
-                    _dev(row_cursor, 'row_cursor')
-                    _shape(row_cursor.dtype == torch.int64 and row_cursor.numel() == 1, 'seg_meter_update: row_cursor: one int64')
-                rc = self.lib.pvcnn_seg_meter_update(_p(logits), _p(targets), b, c, n, _p(part_ranges), part_ranges.shape[0], int(max_parts),
-                                                     None, _p(rows), _p(row_cursor), rows.shape[0], s)
-        _lib.check(rc, 'seg_meter_update')
+        if part_ranges is None:
+            _shape(counts is not None and counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == 3 * c + 2,
+                   'seg_meter_update: counts (3C+2) int64 expected')
+            tail = (None, 0, 0, counts, None, None, 0)
+        else:
+            _i32(part_ranges, 'part_ranges')
+            _shape(part_ranges.dim() == 2 and part_ranges.shape[1] == 2, 'seg_meter_update: part_ranges (K,2) int32 expected')
+            _i32(rows, 'rows')
+            _shape(rows.dim() == 3 and rows.shape[1:] == (int(max_parts) + 1, 2), 'seg_meter_update: rows (capacity, max_parts+1, 2)')
+            if row_cursor is not None:
+                _dev(row_cursor, 'row_cursor')
+                _shape(row_cursor.dtype == torch.int64 and row_cursor.numel() == 1, 'seg_meter_update: row_cursor: one int64')
+            tail = (part_ranges, part_ranges.shape[0], int(max_parts), None, rows, row_cursor, rows.shape[0])
+        _run(self.lib.pvcnn_seg_meter_update, 'seg_meter_update', logits, logits, targets, b, c, n, *tail)
 
     # ---- oriented boxes (csrc/boxes.hip, ABI v14): meters/kitti and the KITTI AP overlaps on the device ------------------------------
     @staticmethod
@@ -1424,10 +1307,8 @@ class HipBackend:
                and tuple(sres_t.shape) == (b, 3) and cls_t.numel() == b, 'frustum_meter_update: targets of B boxes expected')
         _shape(thresholds.dtype == torch.float64 and thresholds.numel() == k and sums.dtype == torch.float64 and sums.numel() == 2
                and counts.numel() == 3 + 2 * k, 'frustum_meter_update: thresholds (K) / sums (2) float64, counts (3 + 2K) int64')
-        with _Launch(outputs[0]) as s:
-            _lib.check(self.lib.pvcnn_frustum_meter_update(*(_p(t) for t in outputs), *(_p(t) for t in targets), b, nh, ns,
-                                                           _p(bin_centers), _p(size_templates), _p(class_ids), _p(thresholds), k,
-                                                           None, None, 0, 0, _p(sums), _p(counts), s), 'frustum_meter_update')
+        _run(self.lib.pvcnn_frustum_meter_update, 'frustum_meter_update', outputs[0], *outputs, *targets, b, nh, ns, bin_centers,
+             size_templates, class_ids, thresholds, k, None, None, 0, 0, sums, counts)
 
     def frustum_meter_accuracy(self, mask_logits, mask_targets, counts):
         """MeterFrustumKitti.update, metric 'accuracy': counts[0] += B*N, counts[1] += #(argmax(mask_logits, 1) == target)."""
@@ -1437,9 +1318,8 @@ class HipBackend:
                'frustum_meter_accuracy: mask_logits (B,C,N) float32, targets (B,N) int64')
         _shape(counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() >= 2, 'frustum_meter_accuracy: counts int64')
         b, c, n = mask_logits.shape
-        with _Launch(mask_logits) as s:
-            _lib.check(self.lib.pvcnn_frustum_meter_update(*([None] * 11), b, 0, 0, None, None, None, None, 0, _p(mask_logits),
-                                                           _p(mask_targets), c, n, None, _p(counts), s), 'frustum_meter_accuracy')
+        _run(self.lib.pvcnn_frustum_meter_update, 'frustum_meter_accuracy', mask_logits, *([None] * 11), b, 0, 0, None, None, None, None, 0,
+             mask_logits, mask_targets, c, n, None, counts)
 
     def box_iou_3d(self, corners_1, corners_t):
         """(B, 3, 8) float32 corner sets -> (iou_3d, iou_2d), (B) float64 each (get_box_iou_3d per pair)."""
@@ -1449,8 +1329,7 @@ class HipBackend:
         b = corners_1.shape[0]
         iou_3d = torch.empty((b,), dtype=torch.float64, device=corners_1.device)
         iou_2d = torch.empty_like(iou_3d)
-        with _Launch(corners_1) as s:
-            _lib.check(self.lib.pvcnn_box_iou_3d(_p(corners_1), _p(corners_t), b, _p(iou_3d), _p(iou_2d), s), 'box_iou_3d')
+        _run(self.lib.pvcnn_box_iou_3d, 'box_iou_3d', corners_1, corners_1, corners_t, b, iou_3d, iou_2d)
         return iou_3d, iou_2d
 
     def rotate_iou(self, boxes, query_boxes, criterion=-1, boxes_3d=None, query_boxes_3d=None, z_axis=1, z_center=1.0):
@@ -1461,17 +1340,15 @@ class HipBackend:
                'rotate_iou: boxes (N,5) and query_boxes (K,5) expected')
         n, k = boxes.shape[0], query_boxes.shape[0]
         out = torch.zeros((n, k), dtype=torch.float32, device=boxes.device)
-        with _Launch(boxes) as s:
-            if boxes_3d is None:
-                rc = self.lib.pvcnn_rotate_iou(_p(boxes), n, _p(query_boxes), k, int(criterion), _p(out), s)
-            else:
-                for t, name, rows in ((boxes_3d, 'boxes_3d', n), (query_boxes_3d, 'query_boxes_3d', k)):
-                    _dev(t, name)
-                    _shape(t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, 7),
-                           f'box3d_overlap: {name} ({rows},7) contiguous float64 expected')
-                rc = self.lib.pvcnn_box3d_overlap(_p(boxes), _p(boxes_3d), n, _p(query_boxes), _p(query_boxes_3d), k, int(criterion),
-                                                  int(z_axis), float(z_center), _p(out), s)
-        _lib.check(rc, 'rotate_iou' if boxes_3d is None else 'box3d_overlap')
+        if boxes_3d is None:
+            _run(self.lib.pvcnn_rotate_iou, 'rotate_iou', boxes, boxes, n, query_boxes, k, int(criterion), out)
+            return out
+        for t, name, rows in ((boxes_3d, 'boxes_3d', n), (query_boxes_3d, 'query_boxes_3d', k)):
+            _dev(t, name)
+            _shape(t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (rows, 7),
+                   f'box3d_overlap: {name} ({rows},7) contiguous float64 expected')
+        _run(self.lib.pvcnn_box3d_overlap, 'box3d_overlap', boxes, boxes, boxes_3d, n, query_boxes, query_boxes_3d, k, int(criterion),
+             int(z_axis), float(z_center), out)
         return out
 
     def frustum_predictions(self, heads, bin_centers, size_templates, rotation_angle, rgb_score, table, step):
@@ -1485,10 +1362,8 @@ class HipBackend:
         _shape(rotation_angle.numel() == b and rgb_score.numel() == b and table.dim() == 2 and table.shape[1] == 8,
                'frustum_predictions: rotation_angle, rgb_score (B), table (rows, 8) expected')
         _shape(0 <= int(step) and int(step) + b <= table.shape[0], 'frustum_predictions: the batch does not fit in the table')
-        with _Launch(heads[0]) as s:
-            _lib.check(self.lib.pvcnn_frustum_predictions(*(_p(t) for t in heads), b, nh, ns, _p(bin_centers), _p(size_templates),
-                                                          _p(rotation_angle), _p(rgb_score), _p(table), table.shape[0], int(step), s),
-                       'frustum_predictions')
+        _run(self.lib.pvcnn_frustum_predictions, 'frustum_predictions', heads[0], *heads, b, nh, ns, bin_centers, size_templates,
+             rotation_angle, rgb_score, table, table.shape[0], int(step))
 
     # ---- the KITTI AP evaluation (csrc/kitti_ap.hip; include/pvcnn_hip.h "the KITTI AP evaluation") ----
     @staticmethod
@@ -1502,8 +1377,7 @@ class HipBackend:
         n, k = boxes.shape[0], query_boxes.shape[0]
         self._ap_typed(boxes, 'boxes', torch.float64, 4 * n); self._ap_typed(query_boxes, 'query_boxes', torch.float64, 4 * k)
         out = torch.zeros((n, k), dtype=torch.float64, device=boxes.device)
-        with _Launch(boxes) as s:
-            _lib.check(self.lib.pvcnn_image_box_overlap(_p(boxes), n, _p(query_boxes), k, int(criterion), _p(out), s), 'image_box_overlap')
+        _run(self.lib.pvcnn_image_box_overlap, 'image_box_overlap', boxes, boxes, n, query_boxes, k, int(criterion), out)
         return out
 
     def kitti_ap_overlaps(self, p, metric, z_axis=1, z_center=1.0):
@@ -1512,18 +1386,15 @@ class HipBackend:
         dev = p.gt_off.device
         if metric == 0:
             out = torch.zeros((p.pairs,), dtype=torch.float64, device=dev)
-            with _Launch(p.gt_off) as s:
-                _lib.check(self.lib.pvcnn_kitti_ap_bbox_overlaps(_p(p.dt_bbox), _p(p.gt_bbox), _p(p.dt_off), _p(p.gt_off), _p(p.pair_off),
-                                                                 p.images, p.pairs, _p(out), s), 'kitti_ap_bbox_overlaps')
+            _run(self.lib.pvcnn_kitti_ap_bbox_overlaps, 'kitti_ap_bbox_overlaps', p.gt_off, p.dt_bbox, p.gt_bbox, p.dt_off, p.gt_off,
+                 p.pair_off, p.images, p.pairs, out)
             return out
         _shape(metric in (1, 2), 'unknown metric')
         bev_dt, bev_gt, full_dt, full_gt = p.boxes_3d(z_axis)
         out = torch.zeros((p.pairs,), dtype=torch.float32, device=dev)
         full = (None, None) if metric == 1 else (full_dt, full_gt)
-        with _Launch(p.gt_off) as s:
-            _lib.check(self.lib.pvcnn_kitti_ap_box_overlaps(_p(bev_dt), _p(full[0]), _p(bev_gt), _p(full[1]), _p(p.dt_off), _p(p.gt_off),
-                                                            _p(p.pair_off), p.images, p.pairs, -1, int(z_axis), float(z_center), _p(out), s),
-                       'kitti_ap_box_overlaps')
+        _run(self.lib.pvcnn_kitti_ap_box_overlaps, 'kitti_ap_box_overlaps', p.gt_off, bev_dt, full[0], bev_gt, full[1], p.dt_off, p.gt_off,
+             p.pair_off, p.images, p.pairs, -1, int(z_axis), float(z_center), out)
         return out
 
     def kitti_ap_clean(self, p, classes, difficulties):
@@ -1537,11 +1408,8 @@ class HipBackend:
         dc_index = torch.zeros((p.dontcares,), dtype=torch.int32, device=dev)
         dc_out = self._ap_some(dc_index)
         num_valid_gt = torch.zeros((m, l), dtype=torch.int64, device=dev)
-        with _Launch(p.gt_off) as s:
-            _lib.check(self.lib.pvcnn_kitti_ap_clean(_p(p.gt_name), _p(p.gt_bbox), _p(p.gt_occluded), _p(p.gt_truncated), p.G, _p(p.dt_name),
-                                                     _p(p.dt_bbox), p.D, _p(p.gt_off), _p(p.dc_off), p.images, _p(classes), m,
-                                                     _p(difficulties), l, _p(ignored_gt), _p(ignored_det), _p(dc_out), _p(num_valid_gt), s),
-                       'kitti_ap_clean')
+        _run(self.lib.pvcnn_kitti_ap_clean, 'kitti_ap_clean', p.gt_off, p.gt_name, p.gt_bbox, p.gt_occluded, p.gt_truncated, p.G, p.dt_name,
+             p.dt_bbox, p.D, p.gt_off, p.dc_off, p.images, classes, m, difficulties, l, ignored_gt, ignored_det, dc_out, num_valid_gt)
         return ignored_gt, ignored_det, dc_index, num_valid_gt
 
     @staticmethod
@@ -1558,17 +1426,15 @@ class HipBackend:
         self._ap_typed(ignored_gt, 'ignored_gt', torch.int8, m * l * p.G); self._ap_typed(ignored_det, 'ignored_det', torch.int8, m * l * p.D)
         self._ap_typed(dc_index, 'dc_index', torch.int32, p.dontcares)
         overlaps, dc_index = self._ap_some(overlaps), self._ap_some(dc_index)
-        return (_p(overlaps), _p(p.gt_off), _p(p.dt_off), _p(p.dc_off), _p(p.pair_off), p.images, p.G, p.D, p.max_gt, p.max_dt,
-                _p(ignored_gt), _p(ignored_det), _p(p.dt_score), _p(p.dt_alpha), _p(p.gt_alpha), _p(p.dt_bbox), _p(p.gt_bbox), _p(dc_index),
-                _p(min_overlaps), m, l, k), (m, l, k)
+        return (overlaps, p.gt_off, p.dt_off, p.dc_off, p.pair_off, p.images, p.G, p.D, p.max_gt, p.max_dt, ignored_gt, ignored_det,
+                p.dt_score, p.dt_alpha, p.gt_alpha, p.dt_bbox, p.gt_bbox, dc_index, min_overlaps, m, l, k), (m, l, k)
 
     def kitti_ap_match(self, p, overlaps, clean, min_overlaps):
         """Matching pass 1 for every (image, class, difficulty, min_overlap row): tp_scores (M, L, K, G) float64, a true positive's
         score in the slot of its ground truth and -inf elsewhere.  overlaps: float64, flat at p.pair_off; min_overlaps (K, M)."""
         args, cells = self._ap_args(p, overlaps, clean, min_overlaps)
         tp_scores = torch.full(cells + (p.G,), float('-inf'), dtype=torch.float64, device=overlaps.device)
-        with _Launch(p.gt_off) as s:
-            _lib.check(self.lib.pvcnn_kitti_ap_match(*args, _p(tp_scores), s), 'kitti_ap_match')
+        _run(self.lib.pvcnn_kitti_ap_match, 'kitti_ap_match', p.gt_off, *args, tp_scores)
         return tp_scores
 
     def kitti_ap_thresholds(self, tp_scores, num_valid_gt):
@@ -1578,9 +1444,7 @@ class HipBackend:
         ordered = torch.sort(tp_scores, dim=-1, descending=True).values.contiguous()
         thresholds = torch.zeros((m, l, k, 41), dtype=torch.float64, device=tp_scores.device)
         counts = torch.zeros((m, l, k), dtype=torch.int32, device=tp_scores.device)
-        with _Launch(tp_scores) as s:
-            _lib.check(self.lib.pvcnn_kitti_ap_thresholds(_p(ordered), g, _p(num_valid_gt), m * l * k, k, _p(thresholds), _p(counts), s),
-                       'kitti_ap_thresholds')
+        _run(self.lib.pvcnn_kitti_ap_thresholds, 'kitti_ap_thresholds', tp_scores, ordered, g, num_valid_gt, m * l * k, k, thresholds, counts)
         return thresholds, counts
 
     def kitti_ap_stats(self, p, overlaps, clean, min_overlaps, thresholds, counts, metric, compute_aos):
@@ -1591,9 +1455,8 @@ class HipBackend:
         pr = torch.zeros(cells + (41, 4), dtype=torch.float64, device=overlaps.device)
         nbytes = self.lib.pvcnn_kitti_ap_workspace_bytes(p.images, n)
         workspace = torch.empty((max(nbytes, 8) // 8,), dtype=torch.float64, device=overlaps.device)
-        with _Launch(p.gt_off) as s:
-            _lib.check(self.lib.pvcnn_kitti_ap_stats(*args, _p(thresholds), _p(counts), int(metric), int(bool(compute_aos)), _p(pr),
-                                                     _p(workspace), nbytes, s), 'kitti_ap_stats')
+        _run(self.lib.pvcnn_kitti_ap_stats, 'kitti_ap_stats', p.gt_off, *args, thresholds, counts, int(metric), int(bool(compute_aos)), pr,
+             workspace, nbytes)
         return pr
 
 
@@ -1706,8 +1569,7 @@ class _WeightBank:
         lib = self.be.lib
         for (kind, nsplit), (table, n, rows, keys, dev) in self.tables.items():
             launch = self._PRODUCTS[kind].entry(lib, 'weight_split_pair_batch' + self._PAIR_SUFFIX[nsplit])
-            with _Launch(table) as s:
-                _lib.check(launch(_p(table), n, rows, s), 'weight_split_pair_batch')
+            _run(launch, 'weight_split_pair_batch', table, table, n, rows)
             if capturing:                               # the captured launch walks this table and writes every entry's buffers on replay
                 self.pinned.append(table)
             for key in keys:

@@ -15,13 +15,13 @@ from torch.autograd import Function
 
 from . import _cache, _gradslots
 from ._autograd import native, amp_fwd, amp_bwd
+from .backend import batch_strided_ok
 from .devoxelization import CornerTaps
 
 
 def _rows(t, shape):
     """grad tensor -> (B, C, S) view without a copy when each sample's rows are contiguous (channel slices of a
     wider tensor, as torch.cat's backward produces), else a contiguous copy."""
-    from .backend import batch_strided_ok
     if t.dim() == len(shape) and t.dim() >= 3:
         try:
             v = t.view(shape[0], shape[1], -1) if t.dim() > 3 else t
@@ -67,9 +67,26 @@ def _bnact_backward(x3, g3, w, b, mean, rstd, slope, training, shape, drop=None)
     if seg:
         gx, gw, gb, amax = be.bnact_backward(x3, g3, w, b, mean, rstd, slope, training, amax_seg=seg, **({'drop': drop} if drop else {}), **dst)
         return _cache.tag_amax(gx.view(shape), seg, amax), gw, gb
-    assert drop is None, 'the fused dropout rides on the amax-emitting passes'  
+    assert drop is None, 'the fused dropout rides on the amax-emitting passes'
     gx, gw, gb = be.bnact_backward(x3, g3, w, b, mean, rstd, slope, training, **dst)
     return gx.view(shape), gw, gb
+
+
+def _prologue(x, weight, bias):
+    """-> (x's shape, x as a contiguous (B, C, S) view, gamma and beta made contiguous | None) of a node's forward."""
+    return (x.shape, x.contiguous().view(x.shape[0], x.shape[1], -1), weight.contiguous() if weight is not None else None,
+            bias.contiguous() if bias is not None else None)
+
+
+def _statistics(x3, use_batch_stats, stats_part, stats_shift, running_mean, running_var, momentum, eps, counter, zero_word=None):
+    """-> (mean, rstd) of x3 (B, C, S): finalised from the partial sums of the producing convolution's epilogue (zero_word: a buffer
+    that launch also zeroes; counter: num_batches_tracked, incremented by it), else measured by a pass over x3, else the running ones."""
+    if use_batch_stats and stats_part is not None:
+        return native().bn_finalize(stats_part, x3.shape[0] * x3.shape[2], running_mean, running_var, momentum, eps, stats_shift,
+                                    **({'zero_word': zero_word} if zero_word is not None else {}), counter=counter)
+    if use_batch_stats:
+        return native().bn_stats(x3, running_mean, running_var, momentum, eps)
+    return running_mean.contiguous(), torch.rsqrt(running_var + eps)
 
 
 __all__ = ['batch_norm_act', 'batch_norm_act_devoxelize', 'batch_norm_act_se_devoxelize', 'fusable_tail', 'run_layers', 'fused_dropout_ok']
@@ -84,16 +101,15 @@ class BatchNormAct(Function):
         drop_p > 0 (with amax_seg > 0): y = dropout(act(bn(x)), drop_p) with the keep decisions of csrc/bnact.hip under drop_seed.
         row_max (amax_seg > 0, statistics from an epilogue, no dropout): -> (y, amax, winners, values), the last two == y.max(dim=-1)'s
         indices and values, emitted by the apply pass (emit_row_max)."""
-        shape = x.shape
-        x3 = x.contiguous().view(shape[0], shape[1], -1)
-        w = weight.contiguous() if weight is not None else None
-        b = bias.contiguous() if bias is not None else None
-        stats = armed = None
+        shape, x3, w, b = _prologue(x, weight, bias)
+        stats = whole = armed = keys = None
         if training and stats_part is not None:   # partial sums from the producing convolution's epilogue
-            if amax_seg and row_max:              # ... and zeroes the row keys of the max-pool that follows, in the same buffer
+            if amax_seg and row_max:              # the finalize launch also zeroes the row keys of the max-pool that follows, in the same buffer
                 whole, armed, keys = native().amax_and_row_keys(x3.shape[0], x3.shape[1], x3.shape[2], amax_seg, x3.device)
-                stats = native().bn_finalize(stats_part, x3.shape[0] * x3.shape[2], running_mean, running_var, momentum, eps, stats_shift,
-                                             zero_word=whole, counter=counter)
+            elif amax_seg:                        # ... or arms word [0] of the amax buffer the apply pass fills
+                whole = armed = native().amax_buffer(x3.shape[0], x3.shape[2], amax_seg, x3.device)
+            stats = _statistics(x3, True, stats_part, stats_shift, running_mean, running_var, momentum, eps, counter, zero_word=whole)
+            if keys is not None:
                 ctx.slope, ctx.training, ctx.shape, ctx.drop = slope, training, shape, None
                 dest = getattr(_ROW_MAX, 'out', None)       # (emit_row_max(bn, out=...): y goes straight into its slice of the concatenation)
                 if dest is not None and not (dest.is_cuda and tuple(dest.shape) == tuple(x3.shape) and dest.dtype == torch.float32):
@@ -103,13 +119,6 @@ class BatchNormAct(Function):
                 ctx.mark_non_differentiable(armed, winners, values)
                 ctx.set_materialize_grads(False)
                 return y.view(shape), armed, winners, values
-            if amax_seg:                          # the finalize launch also arms word [0] of the amax buffer the apply pass fills
-                armed = native().amax_buffer(x3.shape[0], x3.shape[2], amax_seg, x3.device)
-                stats = native().bn_finalize(stats_part, x3.shape[0] * x3.shape[2], running_mean, running_var, momentum, eps, stats_shift,
-                                             zero_word=armed, counter=counter)
-            else:
-                stats = native().bn_finalize(stats_part, x3.shape[0] * x3.shape[2], running_mean, running_var, momentum, eps, stats_shift,
-                                             counter=counter)
         ctx.slope, ctx.training, ctx.shape = slope, training, shape
         ctx.drop = (drop_seed, float(drop_p)) if (drop_p and drop_seed is not None) else None
         if amax_seg:
@@ -131,8 +140,7 @@ class BatchNormAct(Function):
         x3, w, b, mean, rstd = ctx.saved_tensors
         g3 = _rows(grad_y, ctx.shape)
         gx, gw, gb = _bnact_backward(x3, g3, w, b, mean, rstd, ctx.slope, ctx.training, ctx.shape, drop=ctx.drop)
-        return (gx, gw if w is not None else None, gb if b is not None else None,
-                None, None, None, None, None, None, None, None, None, None, None, None, None)
+        return (gx, gw if w is not None else None, gb if b is not None else None) + (None,) * 13
 
 
 # ---- the max-pool over the points behind a (BatchNorm, activation) pair, emitted by the pair's apply pass ----------------------------
@@ -185,6 +193,11 @@ def _split(stats):
     return part, (shift.detach().contiguous() if shift is not None else None)
 
 
+def _module_call(bn, stats_part):
+    """What the three wrappers hand their node: -> (*_bn_mode(bn): use_batch_stats, momentum, rm, rv, counter; *_split(stats_part): part, shift)."""
+    return (*_bn_mode(bn, finalize_counts=stats_part is not None and bn.training), *_split(stats_part))
+
+
 def fused_dropout_ok(x):
     """Can an nn.Dropout in training mode behind a (BatchNorm, activation) pair over x ride on the pair's passes (batch_norm_act(...,
     drop_p=p))?  Needs the amax-emitting passes (csrc/bnact.hip) -- i.e. the f16x2 arithmetic of the convolution next door -- and no
@@ -199,8 +212,7 @@ def batch_norm_act(x, bn, slope, stats_part=None, drop_p=0.0):
     drop_p > 0 (only where fused_dropout_ok(x)): ... followed by a training-mode nn.Dropout(drop_p), in the same passes; the keep
     decisions are a function of one int64 drawn here from torch's generator (so torch.manual_seed governs them, and a captured graph
     draws a fresh one per replay) -- a different stream than torch.nn.functional.dropout's, the same distribution."""
-    use_batch_stats, momentum, rm, rv, counter = _bn_mode(bn, finalize_counts=stats_part is not None and bn.training)
-    part, shift = _split(stats_part)
+    use_batch_stats, momentum, rm, rv, counter, part, shift = _module_call(bn, stats_part)
     # the apply pass emits the f16x2 scale table of what it writes for the convolution that (usually) consumes it
     seg = _amax_seg_for(x.shape, x.is_cuda)
     if (seg and bn is getattr(_ROW_MAX, 'bn', None) and not drop_p and use_batch_stats and part is not None and x.dim() == 3
@@ -228,17 +240,8 @@ class BatchNormActDevoxelize(Function):
     @amp_fwd
     def forward(ctx, grid, coords, weight, bias, running_mean, running_var, use_batch_stats, momentum, eps, slope,
                 resolution, is_training, stats_part=None, stats_shift=None, addend=None, counter=None):
-        shape = grid.shape
-        x3 = grid.contiguous().view(shape[0], shape[1], -1)
-        w = weight.contiguous() if weight is not None else None
-        b = bias.contiguous() if bias is not None else None
-        if use_batch_stats and stats_part is not None:
-            mean, rstd = native().bn_finalize(stats_part, x3.shape[0] * x3.shape[2], running_mean, running_var, momentum, eps, stats_shift,
-                                              counter=counter)
-        elif use_batch_stats:
-            mean, rstd = native().bn_stats(x3, running_mean, running_var, momentum, eps)
-        else:
-            mean, rstd = running_mean.contiguous(), torch.rsqrt(running_var + eps)
+        shape, x3, w, b = _prologue(grid, weight, bias)
+        mean, rstd = _statistics(x3, use_batch_stats, stats_part, stats_shift, running_mean, running_var, momentum, eps, counter)
         r = int(resolution)
         pts = coords.contiguous()
         add = addend.contiguous() if addend is not None else None      # the point branch: added in the gather's store
@@ -258,16 +261,43 @@ class BatchNormActDevoxelize(Function):
         x3, w, b, mean, rstd, _, _ = ctx.saved_tensors
         g_act = ctx.taps.backward(_rows(grad_out, grad_out.shape))
         gx, gw, gb = _bnact_backward(x3, g_act.view(x3.shape), w, b, mean, rstd, ctx.slope, ctx.use_batch_stats, ctx.shape)
-        return (gx, None, gw if w is not None else None, gb if b is not None else None,
-                None, None, None, None, None, None, None, None, None, None, grad_out if ctx.has_addend else None, None)
+        return (gx, None, gw if w is not None else None, gb if b is not None else None) + (None,) * 10 + (grad_out if ctx.has_addend else None, None)
 
 
 def batch_norm_act_devoxelize(grid, coords, bn, slope, resolution, is_training, stats_part=None, addend=None):
     """trilinear_devoxelize(act(bn(grid)), coords) [+ addend]: PVConv's tail (modules/pvconv.py:25-27,36-38) in one gather."""
-    use_batch_stats, momentum, rm, rv, counter = _bn_mode(bn, finalize_counts=stats_part is not None and bn.training)
-    part, shift = _split(stats_part)
+    use_batch_stats, momentum, rm, rv, counter, part, shift = _module_call(bn, stats_part)
     return BatchNormActDevoxelize.apply(grid, coords, bn.weight, bn.bias, rm, rv, use_batch_stats, momentum, bn.eps, slope,
                                         resolution, is_training, part, shift, addend, counter)
+
+
+def _se_excite_forward(sums, gamma, beta, w1, w2, s3):
+    """backend.se_excite_forward in torch, on sums = (A, Ax) (B, C) each (bnact_partial_sums with grad_y None) instead of their slice sums."""
+    a_sum, ax_sum = sums
+    gam = gamma if gamma is not None else torch.ones_like(a_sum[0])
+    bet = beta if beta is not None else torch.zeros_like(a_sum[0])
+    squeezed = (gam * ax_sum + bet * a_sum) / float(s3)
+    hidden = torch.relu(squeezed @ w1.t())
+    excite = torch.sigmoid(hidden @ w2.t()).contiguous()                                 # (B, C)
+    return a_sum, ax_sum, squeezed, hidden, excite
+
+
+def _se_excite_backward(sums, a_sum, ax_sum, gamma, beta, squeezed, hidden, excite, w1, w2, s3):
+    """backend.se_excite_backward in torch, on sums = (P, Q) (B, C) each (bnact_partial_sums of grad_y) instead of their slice sums."""
+    p_sum, q_sum = sums
+    gam = gamma if gamma is not None else torch.ones_like(p_sum[0])
+    bet = beta if beta is not None else torch.zeros_like(p_sum[0])
+    # excitation backward: s = sigmoid(relu(m W1^T) W2^T)
+    g_excite = gam * q_sum + bet * p_sum
+    g_pre2 = g_excite * excite * (1.0 - excite)
+    g_w2 = g_pre2.t() @ hidden
+    g_pre1 = (g_pre2 @ w2) * (hidden > 0).to(hidden.dtype)
+    g_w1 = g_pre1.t() @ squeezed
+    g_mean = ((g_pre1 @ w1) / float(s3)).contiguous()                                    # dL/d(squeezed) spread over the S voxels
+    # BatchNorm sums of g' = (excite * g_y + g_mean) * act'(z), from the four per-(cloud, channel) sums
+    sum_beta = (excite * p_sum + g_mean * a_sum).sum(dim=0).contiguous()
+    sum_gamma = (excite * q_sum + g_mean * ax_sum).sum(dim=0).contiguous()
+    return g_w1, g_w2, g_mean, sum_beta, sum_gamma
 
 
 class BatchNormActSEDevoxelize(Function):
@@ -291,30 +321,14 @@ class BatchNormActSEDevoxelize(Function):
     def forward(ctx, grid, coords, weight, bias, running_mean, running_var, use_batch_stats, momentum, eps, slope,
                 resolution, is_training, stats_part, stats_shift, addend, counter, fc1, fc2):
         be = native()
-        shape = grid.shape
-        x3 = grid.contiguous().view(shape[0], shape[1], -1)
-        nb, nc, s3 = x3.shape
-        w = weight.contiguous() if weight is not None else None
-        b = bias.contiguous() if bias is not None else None
-        if use_batch_stats and stats_part is not None:
-            mean, rstd = be.bn_finalize(stats_part, nb * s3, running_mean, running_var, momentum, eps, stats_shift, counter=counter)
-        elif use_batch_stats:
-            mean, rstd = be.bn_stats(x3, running_mean, running_var, momentum, eps)
-        else:
-            mean, rstd = running_mean.contiguous(), torch.rsqrt(running_var + eps)
-        # squeeze from the two sums (grad_y == 1 in the reduction kernel of the BatchNorm backward)
+        shape, x3, w, b = _prologue(grid, weight, bias)
+        mean, rstd = _statistics(x3, use_batch_stats, stats_part, stats_shift, running_mean, running_var, momentum, eps, counter)
+        # squeeze from the two sums (grad_y == 1 in the reduction kernel of the BatchNorm backward): the slice sums of the pass + the
+        # excitation in one launch (csrc/se.hip) where the kernel serves the sizes, else the (B, C) sums and torch
         w1, w2 = fc1.contiguous(), fc2.contiguous()
-        fused_se = getattr(be, 'has_se_excite', False) and nc <= 2048 and w1.shape[0] <= 256
-        if fused_se:     # the slice sums of the pass + the excitation: one launch (csrc/se.hip)
-            part = be.bnact_partial_sums_raw(x3, None, w, b, mean, rstd, slope)
-            a_sum, ax_sum, squeezed, hidden, excite = be.se_excite_forward(part, w, b, w1, w2, s3)
-        else:
-            a_sum, ax_sum = be.bnact_partial_sums(x3, None, w, b, mean, rstd, slope)        # (B, C) each
-            gam = w if w is not None else torch.ones_like(mean)
-            bet = b if b is not None else torch.zeros_like(mean)
-            squeezed = (gam * ax_sum + bet * a_sum) / float(s3)
-            hidden = torch.relu(squeezed @ w1.t())
-            excite = torch.sigmoid(hidden @ w2.t()).contiguous()                             # (B, C)
+        fused = ctx.fused_se = getattr(be, 'has_se_excite', False) and x3.shape[1] <= 2048 and w1.shape[0] <= 256
+        sums = (be.bnact_partial_sums_raw if fused else be.bnact_partial_sums)(x3, None, w, b, mean, rstd, slope)
+        a_sum, ax_sum, squeezed, hidden, excite = (be.se_excite_forward if fused else _se_excite_forward)(sums, w, b, w1, w2, x3.shape[2])
         r = int(resolution)
         pts = coords.contiguous()
         add = addend.contiguous() if addend is not None else None
@@ -333,40 +347,24 @@ class BatchNormActSEDevoxelize(Function):
     def backward(ctx, grad_out):
         be = native()
         x3, w, b, mean, rstd, a_sum, ax_sum, squeezed, hidden, excite, w1, w2, _, _ = ctx.saved_tensors
-        nb, nc, s3 = x3.shape
         g_y = ctx.taps.backward(_rows(grad_out, grad_out.shape)).view(x3.shape)             # dL/d(act(bn(x)) * excite)
-        if getattr(be, 'has_se_excite', False) and nc <= 2048 and w1.shape[0] <= 256:
-            # the slice sums P, Q + the excitation backward + the BatchNorm sums below in two launches (csrc/se.hip)
-            part = be.bnact_partial_sums_raw(x3, g_y, w, b, mean, rstd, ctx.slope)
-            g_w1, g_w2, g_mean, sum_beta, sum_gamma = be.se_excite_backward(part, a_sum, ax_sum, w, b, squeezed, hidden, excite, w1, w2, s3)
-        else:
-            p_sum, q_sum = be.bnact_partial_sums(x3, g_y, w, b, mean, rstd, ctx.slope)      # (B, C) each
-            gam = w if w is not None else torch.ones_like(mean)
-            bet = b if b is not None else torch.zeros_like(mean)
-            # excitation backward: s = sigmoid(relu(m W1^T) W2^T)
-            g_excite = gam * q_sum + bet * p_sum
-            g_pre2 = g_excite * excite * (1.0 - excite)
-            g_w2 = g_pre2.t() @ hidden
-            g_pre1 = (g_pre2 @ w2) * (hidden > 0).to(hidden.dtype)
-            g_w1 = g_pre1.t() @ squeezed
-            g_mean = ((g_pre1 @ w1) / float(s3)).contiguous()                                # dL/d(squeezed) spread over the S voxels
-            # BatchNorm sums of g' = (excite * g_y + g_mean) * act'(z), from the four per-(cloud, channel) sums
-            sum_beta = (excite * p_sum + g_mean * a_sum).sum(dim=0).contiguous()
-            sum_gamma = (excite * q_sum + g_mean * ax_sum).sum(dim=0).contiguous()
+        # the slice sums P, Q + the excitation backward + the BatchNorm sums in two launches (csrc/se.hip), or the (B, C) sums and torch
+        sums = (be.bnact_partial_sums_raw if ctx.fused_se else be.bnact_partial_sums)(x3, g_y, w, b, mean, rstd, ctx.slope)
+        g_w1, g_w2, g_mean, sum_beta, sum_gamma = (be.se_excite_backward if ctx.fused_se else _se_excite_backward)(
+            sums, a_sum, ax_sum, w, b, squeezed, hidden, excite, w1, w2, x3.shape[2])
         seg = _amax_seg_for(ctx.shape, x3.is_cuda) or 256
         gx, amax = be.bnact_backward_apply(x3, g_y, w, b, mean, rstd, sum_gamma, sum_beta, ctx.slope, ctx.use_batch_stats,
                                            bc_mul=excite, bc_add=g_mean, amax_seg=seg)
         gx = gx.view(ctx.shape)
         if _amax_seg_for(ctx.shape, x3.is_cuda):
             _cache.tag_amax(gx, seg, amax)
-        return (gx, None, sum_gamma if w is not None else None, sum_beta if b is not None else None,
-                None, None, None, None, None, None, None, None, None, None, grad_out if ctx.has_addend else None, None, g_w1, g_w2)
+        return ((gx, None, sum_gamma if w is not None else None, sum_beta if b is not None else None) + (None,) * 10
+                + (grad_out if ctx.has_addend else None, None, g_w1, g_w2))
 
 
 def batch_norm_act_se_devoxelize(grid, coords, bn, slope, se, resolution, is_training, stats_part=None, addend=None):
     """trilinear_devoxelize(se(act(bn(grid))), coords) [+ addend]: PVConv's tail with squeeze-and-excitation in one node."""
-    use_batch_stats, momentum, rm, rv, counter = _bn_mode(bn, finalize_counts=stats_part is not None and bn.training)
-    part, shift = _split(stats_part)
+    use_batch_stats, momentum, rm, rv, counter, part, shift = _module_call(bn, stats_part)
     return BatchNormActSEDevoxelize.apply(grid, coords, bn.weight, bn.bias, rm, rv, use_batch_stats, momentum, bn.eps, slope,
                                           resolution, is_training, part, shift, addend, counter, se.fc[0].weight, se.fc[2].weight)
 

@@ -15,11 +15,10 @@ into the device block the kernel reads.
 
 GPU only (there is no CPU implementation of the kernel); use torch.optim.Adam for CPU runs.
 """
-import ctypes
-
 import torch
 
 from . import _lib
+from .modules.functional.backend import _run
 
 __all__ = ['FlatAdam']
 
@@ -91,18 +90,14 @@ class FlatAdam(torch.optim.Optimizer):
                 loss = closure()
         if len(self.param_groups) != 1:
             raise RuntimeError('FlatAdam updates one parameter group')
-        vp = ctypes.c_void_p
         last = len(self.reducer.buckets) - 1
-        dev = self.step_count.device
-        with torch.cuda.device(dev):
+        with torch.cuda.device(self.step_count.device):
             if not torch.cuda.is_current_stream_capturing():
                 self._check_aliasing()
                 self.sync_hyperparameters()
-            stream = vp(torch.cuda.current_stream(dev).cuda_stream)
             for i, b in enumerate(self.reducer.buckets):
-                _lib.check(self._lib.pvcnn_adam_step(vp(b.pflat.data_ptr()), vp(b.flat.data_ptr()), vp(self.exp_avg[i].data_ptr()),
-                                                     vp(self.exp_avg_sq[i].data_ptr()), b.flat.numel(), vp(self.step_count.data_ptr()),
-                                                     vp(self.hyper.data_ptr()), int(i == last), stream), 'adam_step')
+                _run(self._lib.pvcnn_adam_step, 'adam_step', self.step_count, b.pflat, b.flat, self.exp_avg[i], self.exp_avg_sq[i],
+                     b.flat.numel(), self.step_count, self.hyper, int(i == last))
         # the kernel writes the parameters through raw pointers: torch's version counters do not move, so tell the holders of
         # derived data (the f16x2 weight images of backend.weight_bank_*) that every parameter changed
         from .modules.functional._autograd import native

@@ -20,7 +20,6 @@ Both go through `_read`, which counts them (`copies_made()`).
 
 The product path needs device tensors (or numpy arrays, uploaded once) and the native library: there is no CPU implementation.
 """
-import ctypes
 import math
 
 import numpy as np
@@ -28,7 +27,7 @@ import torch
 
 from . import _lib
 from .evaluate import SceneVotes, s3dis_file_votes
-from .modules.functional.backend import _Launch
+from .modules.functional.backend import _run
 
 __all__ = ['RoomWindows', 'prepare_room', 'segment_room', 'copies_made', 'COPIES_PER_PASS']
 
@@ -51,21 +50,10 @@ def _read(t):
 
 def _call(name, ref, *args):
     """One pvcnn_room_* call on `ref`'s device and torch's current stream: tensors as device pointers, None as NULL, floats as doubles."""
-    lib = _lib.load()
-    conv = []
     for a in args:
-        if isinstance(a, torch.Tensor):
-            if a.device != ref.device or not a.is_contiguous():
-                raise ValueError(f'{name}: contiguous tensors on one device expected')
-            conv.append(ctypes.c_void_p(a.data_ptr()))
-        elif a is None:
-            conv.append(ctypes.c_void_p(None))
-        elif isinstance(a, float):
-            conv.append(ctypes.c_double(a))
-        else:
-            conv.append(int(a))
-    with _Launch(ref) as s:
-        _lib.check(getattr(lib, 'pvcnn_' + name)(*conv, s), name)
+        if isinstance(a, torch.Tensor) and (a.device != ref.device or not a.is_contiguous()):
+            raise ValueError(f'{name}: contiguous tensors on one device expected')
+    _run(getattr(_lib.load(), 'pvcnn_' + name), name, ref, *(a if a is None or isinstance(a, (torch.Tensor, float)) else int(a) for a in args))
 
 
 def _device_points(xyzrgb):

@@ -277,7 +277,7 @@ def node_log():
 
 
 # ---- the wrapper log --------------------------------------------------------------------------------------------------------------
-HOST_ONLY = ('_bytes', '_stats_parts', '_count', '_route')       # + *_pair_entry*: fills a host table
+HOST_ONLY = ('_bytes', '_stats_parts', '_count', '_route', '_slices', '_supported', '_grad_floats')       # + *_pair_entry*: fills a host table
 
 
 class ProxyLib:
@@ -305,13 +305,21 @@ class LibRecorder:
         self.named = {t.data_ptr(): name for name, t in named.items() if isinstance(t, torch.Tensor) and t.numel()}
         self.held = list(named.values())
 
+    def noting(self, make):
+        """torch.empty / zeros / full / empty_like as backend.py calls it, with every buffer it makes noted as one of the method's own."""
+        def made(*args, **kwargs):
+            t = make(*args, **kwargs)
+            if t.numel():
+                self.allocated[t.data_ptr()] = (t, t.numel(), str(t.dtype))       # (kept alive: an address is never handed out twice)
+            return t
+        return made
+
     def empty(self, *args, **kwargs):
-        t = self._torch_empty(*args, **kwargs)
-        if t.numel():
-            self.allocated[t.data_ptr()] = (t, t.numel(), str(t.dtype))       # (kept alive: an address is never handed out twice)
-        return t
+        return self.noting(self._torch_empty)(*args, **kwargs)
 
     def role(self, a):
+        if isinstance(a, ctypes.Array):         # a host table of pointers (each by its role) or of integers
+            return [self.role(ctypes.c_void_p(v)) if a._type_ is ctypes.c_void_p else v for v in a]
         if not isinstance(a, ctypes.c_void_p):
             return a if a is None or isinstance(a, (bool, int, float)) else repr(a)
         if a.value is None:
@@ -360,7 +368,8 @@ class _Shim:
 @contextlib.contextmanager
 def proxied_backend():
     """A HipBackend whose `lib` is the proxy, with CPU tensors let through and a null stream -> (backend, recorder).  The module's
-    own names `torch` and `_lib` are shims whose `empty` / `check` report to the recorder."""
+    own names `torch` and `_lib` are shims whose `empty` (`zeros`, `full`, `empty_like`) / `check` report to the recorder; no stream
+    is ever being captured."""
     from pvcnn_amd import _lib
     from pvcnn_amd.modules.functional import backend as mod
     rec = LibRecorder()
@@ -368,7 +377,9 @@ def proxied_backend():
     be._lib = ProxyLib(_lib.load(), rec)
     rec._torch_empty = torch.empty
     saved = (mod._dev, mod._Launch, mod._lib, mod.torch)
-    mod._dev, mod._Launch, mod._lib, mod.torch = (lambda t, name: None), _NullLaunch, _Shim(_lib, check=rec.check), _Shim(torch, empty=rec.empty)
+    shim = _Shim(torch, empty=rec.empty, cuda=_Shim(torch.cuda, is_current_stream_capturing=lambda: False),
+                 **{name: rec.noting(getattr(torch, name)) for name in ('zeros', 'full', 'empty_like')})
+    mod._dev, mod._Launch, mod._lib, mod.torch = (lambda t, name: None), _NullLaunch, _Shim(_lib, check=rec.check), shim
     try:
         yield be, rec
     finally:
