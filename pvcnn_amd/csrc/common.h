@@ -42,6 +42,13 @@ struct SplitEntry {
 static_assert(sizeof(SplitEntry) == 80, "ten 8-byte words");
 
 #ifdef __HIPCC__
+// The entry that owns workgroup `blk` of a batched image refresh: a scan of the row_begin column (uniform scalar loads).
+__device__ __forceinline__ SplitEntry split_entry_of(const SplitEntry *__restrict__ tab, int n, long long blk) {
+  int i = 0;
+  while (i + 1 < n && tab[i + 1].row_begin <= blk) ++i;
+  return tab[i];
+}
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for every outstanding GLOBAL store of the
 // wave (s_waitcnt vmcnt(0): its release fence), which serialises "store a tile, barrier, load the next one" loops on the
 // full write latency; kernels whose global stores are never read back in the same launch use this instead, so the stores

@@ -28,10 +28,9 @@
 #include <algorithm>
 
 #include "common.h"
+#include "gemm_epilogue.h"
 
 namespace pvcnn {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int kCoTile = 64;
 
@@ -212,11 +211,9 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const float *__restri
     }
   }
 
-  // ---- epilogue: D[i = co][j = voxel]; lane -> voxel j, register r -> co row ----
-  // One 32-row block at a time: its 16 bias values as one batch of loads, and every accumulator fetched from
-  // its AGPR at the point of use (left to the compiler, all 64 are copied to VGPRs in one block at the loop
-  // exit and the kernel drops from 3 to 2 waves per SIMD).
-  float *yb = y + (size_t)b * Co * R * RR;
+  // ---- epilogue: D[i = co][j = voxel]; lane -> voxel j, register r -> co row; bias and the optional BatchNorm partial sums
+  // (pvcnn_conv3d_fwd_stats) are gemm_tile_epilogue's ----
+  const size_t S = (size_t)R * RR;
   size_t voff[NBW];
   bool vok[NBW];
 #pragma unroll
@@ -227,54 +224,17 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const float *__restri
     vok[nb] = gx < R && gy < R && gz < R;
     voff[nb] = (size_t)gx * RR + (size_t)gy * R + gz;
   }
-  // stats_part != nullptr: per-channel (sum, sum of squares) of this workgroup's outputs ride on the epilogue --
-  // the BatchNorm that follows the convolution then needs no statistics pass over y (bn_finalize combines the
-  // per-workgroup partials in fp64 exactly like bn_stats_kernel's).
-  const bool want_stats = stats_part != nullptr;
-  float2 *stat_lds = reinterpret_cast<float2 *>(lds);       // [4 waves][64 channels]
-  if (want_stats) __syncthreads();                          // all waves are done reading xs / ws
-#pragma unroll
-  for (int mb = 0; mb < 2; ++mb) {
-    float bv[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-      bv[r] = (bias != nullptr && co < Co) ? bias[co] : 0.0f;
-    }
-    float ss[16], qq[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ss[r] = qq[r] = 0.0f;
-#pragma unroll
-    for (int nb = 0; nb < NBW; ++nb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = co0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        float v;
-        asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(acc[mb][nb][r]));
-        if (want_stats) {                                   // statistics of (y - bias): the shift keeps E[a^2] - E[a]^2 well
-          const float m = vok[nb] ? v : 0.0f;               // conditioned when the bias dwarfs the spread (bn_finalize adds it back)
-          ss[r] += m;
-          qq[r] += m * m;
-        }
-        v += bv[r];
-        if (vok[nb] && co < Co) yb[(size_t)co * R * RR + voff[nb]] = v;
-      }
-    if (want_stats) {
-      // lane j ends up with the totals of register (j >> 1) & 15 over its 32 voxels / points
-      const float st = half_wave_sum16(ss, j), qt = half_wave_sum16(qq, j);
-      const int rr = (j >> 1) & 15;
-      if ((j & 1) == 0) stat_lds[wave * kCoTile + mb * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * kh] = make_float2(st, qt);
-    }
-  }
-  if (want_stats) {
-    __syncthreads();
-    if (tid < kCoTile && co0 + tid < Co) {
-      float2 t = stat_lds[tid];
-#pragma unroll
-      for (int w = 1; w < 4; ++w) { t.x += stat_lds[w * kCoTile + tid].x; t.y += stat_lds[w * kCoTile + tid].y; }
-      stats_part[(size_t)(co0 + tid) * gridDim.x + blockIdx.x] = t;
-    }
-  }
+  if (stats_part != nullptr) __syncthreads();               // all waves are done reading xs / ws
+  // Every accumulator is fetched from its AGPR at the point of use, one 32-row block at a time behind that block's batch of bias
+  // loads (left to the compiler, all 64 are copied to VGPRs in one block at the loop exit and the kernel drops from 3 to 2 waves
+  // per SIMD).
+  auto acc_at = [&](int mb, int nb, int r) {
+    float v;
+    asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(acc[mb][nb][r]));
+    return v;
+  };
+  gemm_tile_epilogue<false, 2, NBW, 1, kCoTile>(acc_at, y + (size_t)b * Co * S, S, voff, vok, co0, Co, bias, nullptr, 0, stats_part, gridDim.x,
+                                                blockIdx.x, reinterpret_cast<float2 *>(lds));
 }
 
 template <int TX, int TY, int TZ, int CIC, bool VEC, int NBW>

@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include <string.h>
+#include "gemm_epilogue.h"
 #include "route.h"
 #include "split16.h"
 
@@ -42,23 +43,6 @@ namespace pvcnn {
 
 constexpr int kCoTileB = 64;
 constexpr int kKc = 16;            // input channels per chunk = MFMA K
-
-// round-to-nearest-even fp32 -> bf16 (bits); inputs are finite in this path
-__device__ __forceinline__ uint32_t bf16_bits(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-__device__ __forceinline__ float bf16_value(uint32_t bits) { return __uint_as_float(bits << 16); }
-
-// v -> NS bf16 pieces with v = p0 + p1 + p2 (exactly, up to the last piece's rounding at 2^-24 |v|)
-template <int NS>
-__device__ __forceinline__ void split_bf16(float v, uint32_t (&p)[NS]) {
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    p[s] = bf16_bits(v);
-    if (s + 1 < NS) v = v - bf16_value(p[s]);          // exact: the residual fits fp32
-  }
-}
 
 __global__ __launch_bounds__(512) void absmax_kernel(const float *__restrict__ x, size_t n, uint32_t *__restrict__ out) {
   uint32_t m = 0;
@@ -222,13 +206,10 @@ __global__ __launch_bounds__(256) void conv3d_weight_split_f16_pair_kernel(const
 }
 
 // ... of EVERY registered weight of a model in one launch (the weights change once per optimizer step: 7 launches of this kind per PVCNN
-// step, 25 per PVCNN++ step become one).  The entry of a workgroup: a scan of the row_begin column (uniform scalar loads).
+// step, 25 per PVCNN++ step become one).
 __global__ __launch_bounds__(256) void conv3d_weight_split_f16_batch_kernel(const SplitEntry *__restrict__ tab, int n) {
-  const long long blk = blockIdx.x;
-  int i = 0;
-  while (i + 1 < n && tab[i + 1].row_begin <= blk) ++i;
-  const SplitEntry e = tab[i];
-  const int row = (int)(blk - e.row_begin);
+  const SplitEntry e = split_entry_of(tab, n, blockIdx.x);
+  const int row = (int)(blockIdx.x - e.row_begin);
   if (row < (int)e.rows_f) conv3d_weight_split_f16_row(e.w, (int)e.Co, (int)e.Ci, 0, e.wts_f, e.wexp_f, row);
   else conv3d_weight_split_f16_row(e.w, (int)e.Co, (int)e.Ci, 1, e.wts_b, e.wexp_b, row - (int)e.rows_f);
 }
@@ -269,11 +250,8 @@ __global__ __launch_bounds__(256) void conv3d_weight_split_kernel(const float *_
 // conv3d_weight_split_kernel<1> (the Frustum-PVCNN step issued 15 of those).  An entry's rows are 256-element blocks here: rows_f of
 // the forward image first, then the backward-data image; wexp_* are unused (no per-row scale in this arithmetic).
 __global__ __launch_bounds__(256) void conv3d_weight_split_bf16_batch_kernel(const SplitEntry *__restrict__ tab, int n) {
-  const long long blk = blockIdx.x;
-  int i = 0;
-  while (i + 1 < n && tab[i + 1].row_begin <= blk) ++i;
-  const SplitEntry e = tab[i];
-  const long local = (long)(blk - e.row_begin);
+  const SplitEntry e = split_entry_of(tab, n, blockIdx.x);
+  const long local = (long)(blockIdx.x - e.row_begin);
   if (local < (long)e.rows_f) conv3d_weight_split_elem<1>(e.w, (int)e.Co, (int)e.Ci, 0, e.wts_f, local * 256 + threadIdx.x);
   else conv3d_weight_split_elem<1>(e.w, (int)e.Co, (int)e.Ci, 1, e.wts_b, (local - (long)e.rows_f) * 256 + threadIdx.x);
 }
@@ -544,24 +522,7 @@ __global__ __launch_bounds__(256, (NS == 3 || TX * TY * TZ == 512 || TZ <= 16) ?
         load_b(tap, bq[tap & 1]);
       }
       if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);     // or the scheduler sinks the loads to just before their use
-      uint4 (&af)[MBW][NS] = aq[tap % (AD + 1)];
-      uint4 (&bf)[NBW][NS] = bq[tap & 1];
-      // consecutive MFMAs go to different accumulators (4 independent tiles between two partial products of one tile)
-#define PVCNN_MFMA4(SA, SB)                                                                                              \
-      _Pragma("unroll") for (int nb = 0; nb < NBW; ++nb)                                                                 \
-      _Pragma("unroll") for (int mb = 0; mb < MBW; ++mb)                                                                 \
-        acc[mb][nb] = mfma16<NS>(af[mb][SA], bf[nb][SB], acc[mb][nb])
-      if constexpr (NS == 1) {
-        PVCNN_MFMA4(0, 0);
-      } else if constexpr (NS == 2) {
-        PVCNN_MFMA4(1, 0); PVCNN_MFMA4(0, 1);                         // lo x hi, hi x lo, then hi x hi
-        PVCNN_MFMA4(0, 0);
-      } else {
-        PVCNN_MFMA4(2, 0); PVCNN_MFMA4(1, 1); PVCNN_MFMA4(0, 2);      // smallest partial products first
-        PVCNN_MFMA4(1, 0); PVCNN_MFMA4(0, 1);
-        PVCNN_MFMA4(0, 0);
-      }
-#undef PVCNN_MFMA4
+      split_products<NS>(acc, aq[tap % (AD + 1)], bq[tap & 1]);
     }
   }
   if (stats_part != nullptr) __syncthreads();                   // all waves are done reading xs before it is reused below
@@ -578,52 +539,8 @@ __global__ __launch_bounds__(256, (NS == 3 || TX * TY * TZ == 512 || TZ <= 16) ?
     vok[nb] = gx < R && gy < R && gz < R;
     voff[nb] = (size_t)gx * RR + (size_t)gy * R + gz;
   }
-  const bool want_stats = stats_part != nullptr;
-  float2 *stat_lds = reinterpret_cast<float2 *>(lds_u);        // [4 / WM voxel groups][64 channels]
-#pragma unroll
-  for (int mbl = 0; mbl < MBW; ++mbl) {
-    const int mb = wm * MBW + mbl;                              // 32-channel row block inside the 64-channel tile
-    float bv[16], unscale[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-      bv[r] = (bias != nullptr && co < Co) ? bias[co] : 0.0f;
-      if constexpr (NS == 2) unscale[r] = exp2_int(-wexp[co]);   // wexp covers the padded rows of the tile
-    }
-    const float x_unscale = exp2_int(-x_shift);
-    float ss[16], qq[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ss[r] = qq[r] = 0.0f;
-#pragma unroll
-    for (int nb = 0; nb < NBW; ++nb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = co0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        float v = acc[mbl][nb][r];
-        if constexpr (NS == 2) v = v * unscale[r] * x_unscale;  // powers of two: exact
-        if (want_stats) {                                       // statistics of (y - bias), see bn_finalize_kernel
-          const float m = vok[nb] ? v : 0.0f;
-          ss[r] += m;
-          qq[r] += m * m;
-        }
-        v += bv[r];
-        if (vok[nb] && co < Co) yb[(size_t)co * S + voff[nb]] = v;
-      }
-    if (want_stats) {
-      const float st = half_wave_sum16(ss, j), qt = half_wave_sum16(qq, j);
-      const int rr = (j >> 1) & 15;
-      if ((j & 1) == 0) stat_lds[wn * kCoTileB + mb * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * kh] = make_float2(st, qt);
-    }
-  }
-  if (want_stats) {
-    __syncthreads();
-    if (tid < kCoTileB && co0 + tid < Co) {
-      float2 t = stat_lds[tid];
-#pragma unroll
-      for (int w = 1; w < 4 / WM; ++w) { t.x += stat_lds[w * kCoTileB + tid].x; t.y += stat_lds[w * kCoTileB + tid].y; }
-      stats_part[(size_t)(co0 + tid) * gridDim.x + blockIdx.x] = t;
-    }
-  }
+  gemm_tile_epilogue<NS == 2, MBW, NBW, WM, kCoTileB>([&](int mbl, int nb, int r) { return acc[mbl][nb][r]; }, yb, S, voff, vok, co0, Co, bias, wexp,
+                                                      x_shift, stats_part, gridDim.x, blockIdx.x, reinterpret_cast<float2 *>(lds_u));
 }
 
 // ---- the 128-voxel f16x2 tile (TX x TY x 16, R = 16 grids), pipelined ----------------------------------------------------------
@@ -704,11 +621,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const flo
   }
   const int a_row = wm * 32 + j;
   const uint32_t a_off = (uint32_t)(a_row * 8 + ((kh ^ ((a_row >> 3) & 1)) * 4)) * 4u;      // bytes inside one (dz, plane) slab of the image
-  f32x16 acc[NBW];
+  f32x16 acc[1][NBW];                                           // (one row block per wave: the shapes split_products takes)
 #pragma unroll
   for (int nb = 0; nb < NBW; ++nb)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[nb][r] = 0.0f;
+    for (int r = 0; r < 16; ++r) acc[0][nb][r] = 0.0f;
 
   // staging item of this thread: channel octet cg, halo row (hx, hy), z quad q
   const bool has_item = tid < ITEMS;
@@ -762,11 +679,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const flo
     const unsigned char *xt_ = xs + d * TILEB;
     const float next_scale = chunk + 1 < chunks ? item_scale : 0.0f;
     const char *wblk = reinterpret_cast<const char *>(wts + (((size_t)chunk * 9) * cotiles + cot) * WBLK);
-    auto load_a = [&](int tap, uint4 (&af)[NS]) {              // uniform tap base + the lane's 32-bit offset
+    auto load_a = [&](int tap, uint4 (&af)[1][NS]) {           // uniform tap base + the lane's 32-bit offset
       const int dxy = tap / 3, dz = tap - dxy * 3;
       const char *wq = wblk + ((size_t)dxy * cotiles * WBLK + (size_t)dz * NS * kCoTileB * kKc) * sizeof(uint16_t);
 #pragma unroll
-      for (int s = 0; s < NS; ++s) af[s] = *reinterpret_cast<const uint4 *>(wq + s * (kCoTileB * kKc * 2) + a_off);
+      for (int s = 0; s < NS; ++s) af[0][s] = *reinterpret_cast<const uint4 *>(wq + s * (kCoTileB * kKc * 2) + a_off);
     };
     auto load_b = [&](int tap, uint4 (&bf)[NBW][NS]) {
       const int dx = tap / 9, dy = (tap / 3) % 3, dz = tap % 3;
@@ -776,7 +693,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const flo
         for (int s = 0; s < NS; ++s)
           bf[nb][s] = *reinterpret_cast<const uint4 *>(xt_ + bbase[nb][dz] + (s * 2 * HALFB + (dx * HY + dy) * HZ * 16));
     };
-    uint4 aq[AD + 1][NS], bq[2][NBW][NS];
+    uint4 aq[AD + 1][1][NS], bq[2][NBW][NS];
 #pragma unroll
     for (int t = 0; t < AD; ++t) load_a(t, aq[t]);
     load_b(0, bq[0]);
@@ -787,14 +704,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const flo
       if (tap == 24) load_x(min(chunk + 2, chunks - 1), xr);    // behind the chunk's last fragment request
       __builtin_amdgcn_sched_barrier(0);
       if (tap >= 1 && tap <= 7 && (tap & 1)) convert_store(xr, tap >> 1, next_scale, d ^ 1);      // taps 1, 3, 5, 7: z voxel 0..3
-      uint4 (&af)[NS] = aq[tap % (AD + 1)];
-      uint4 (&bf)[NBW][NS] = bq[tap & 1];
-#pragma unroll
-      for (int nb = 0; nb < NBW; ++nb) acc[nb] = mfma16<NS>(af[1], bf[nb][0], acc[nb]);       // lo x hi
-#pragma unroll
-      for (int nb = 0; nb < NBW; ++nb) acc[nb] = mfma16<NS>(af[0], bf[nb][1], acc[nb]);       // hi x lo
-#pragma unroll
-      for (int nb = 0; nb < NBW; ++nb) acc[nb] = mfma16<NS>(af[0], bf[nb][0], acc[nb]);       // hi x hi
+      split_products<NS>(acc, aq[tap % (AD + 1)], bq[tap & 1]);
     }
     __syncthreads();
   }
@@ -811,49 +721,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const flo
     vok[nb] = ox < R && oy < R && zt < R;
     voff[nb] = (size_t)ox * RR + (size_t)oy * R + zt;
   }
-  const bool want_stats = stats_part != nullptr;
-  float2 *stat_lds = reinterpret_cast<float2 *>(lds_u);        // [2 voxel groups][64 channels]
-  {
-    const int mb = wm;
-    float bv[16], unscale[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-      bv[r] = (bias != nullptr && co < Co) ? bias[co] : 0.0f;
-      unscale[r] = exp2_int(-wexp[co]);                         // wexp covers the padded rows of the tile
-    }
-    const float x_unscale = exp2_int(-x_shift);
-    float ss[16], qq[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ss[r] = qq[r] = 0.0f;
-#pragma unroll
-    for (int nb = 0; nb < NBW; ++nb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = co0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        float v = acc[nb][r] * unscale[r] * x_unscale;          // powers of two: exact
-        if (want_stats) {
-          const float m = vok[nb] ? v : 0.0f;
-          ss[r] += m;
-          qq[r] += m * m;
-        }
-        v += bv[r];
-        if (vok[nb] && co < Co) yb[(size_t)co * S + voff[nb]] = v;
-      }
-    if (want_stats) {
-      const float st2 = half_wave_sum16(ss, j), qt = half_wave_sum16(qq, j);
-      const int rr = (j >> 1) & 15;
-      if ((j & 1) == 0) stat_lds[wn * kCoTileB + mb * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * kh] = make_float2(st2, qt);
-    }
-  }
-  if (want_stats) {
-    __syncthreads();
-    if (tid < kCoTileB && co0 + tid < Co) {
-      float2 t = stat_lds[tid];
-      t.x += stat_lds[kCoTileB + tid].x; t.y += stat_lds[kCoTileB + tid].y;
-      stats_part[(size_t)(co0 + tid) * gridDim.x + blockIdx.x] = t;
-    }
-  }
+  gemm_tile_epilogue<true, 1, NBW, 2, kCoTileB>([&](int, int nb, int r) { return acc[0][nb][r]; }, yb, S, voff, vok, co0, Co, bias, wexp, x_shift,
+                                                stats_part, gridDim.x, blockIdx.x, reinterpret_cast<float2 *>(lds_u));
 }
 
 // ---- the 512-voxel f16x2 tile of the R = 32 grids, ONE workgroup per CU, persistent (round 6) -----------------------------------

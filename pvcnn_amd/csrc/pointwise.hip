@@ -165,8 +165,7 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(const float *__restrict__ 
   }
 
   // ---- epilogue: D[i = m][j = point]; lanes = consecutive points (128-byte rows) ----
-  // stats_part != nullptr: per-channel (sum, sum of squares) of this workgroup's outputs ride on the epilogue, so
-  // the BatchNorm that follows needs no statistics pass over y (partials (M, tiles_total), combined by bn_finalize).
+  // FAST / BIAS are compile-time here, so this text stays its own; stats_part follows the contract stated at gemm_tile_epilogue.
   const bool want_stats = stats_part != nullptr;
   float2 *stat_lds = reinterpret_cast<float2 *>(xs);        // [4 waves][TM]
   if (want_stats) __syncthreads();                          // all waves are done reading xs / ws

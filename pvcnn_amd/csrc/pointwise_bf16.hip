@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include <string.h>
+#include "gemm_epilogue.h"
 #include "route.h"
 #include "split16.h"
 
@@ -35,19 +36,6 @@ namespace pvcnn {
 
 constexpr int kPbN = 256;          // points per workgroup
 constexpr int kPbK = 16;           // reduction channels per chunk = MFMA K
-
-__device__ __forceinline__ uint32_t pb_bf16_bits(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-template <int NS>
-__device__ __forceinline__ void pb_split(float v, uint32_t (&p)[NS]) {
-#pragma unroll
-  for (int s = 0; s < NS; ++s) {
-    p[s] = pb_bf16_bits(v);
-    if (s + 1 < NS) v = v - __uint_as_float(p[s] << 16);      // exact residual
-  }
-}
 
 // W (Mo, Ko) fp32 [forward: Mo = Co, Ko = Ci;  for_bwd_data: the GEMM's output channels are Ci and it reduces over Co, W'[ci][co] =
 // W[co][ci]] -> image [chunk][mtile][plane][TM rows][16 k (halves swizzled by bit 3 of the row)] bf16, TM = 32 * MB
@@ -65,7 +53,7 @@ __device__ __forceinline__ void pw_weight_split_elem(const float *__restrict__ w
   float v = 0.0f;
   if (k < KE && m < ME) v = for_bwd_data ? w[(size_t)k * Ci + m] : w[(size_t)m * Ci + k];
   uint32_t p[NS];
-  pb_split<NS>(v, p);
+  split_bf16<NS>(v, p);
   const int pos = ((k_l >> 3) ^ ((row >> 3) & 1)) * 8 + (k_l & 7);
   const size_t blk = ((size_t)chunk * mtiles + mt) * ((size_t)NS * TM * kPbK);
 #pragma unroll
@@ -81,11 +69,8 @@ __global__ __launch_bounds__(256) void pw_weight_split_kernel(const float *__res
 // plain-bf16 (torch.autocast) images of every registered 1x1 weight in one launch (see conv3d_weight_split_bf16_batch_kernel): an
 // entry's rows are 256-element blocks, the forward image's first
 __global__ __launch_bounds__(256) void pw_weight_split_bf16_batch_kernel(const SplitEntry *__restrict__ tab, int n) {
-  const long long blk = blockIdx.x;
-  int i = 0;
-  while (i + 1 < n && tab[i + 1].row_begin <= blk) ++i;
-  const SplitEntry e = tab[i];
-  const long local = (long)(blk - e.row_begin);
+  const SplitEntry e = split_entry_of(tab, n, blockIdx.x);
+  const long local = (long)(blockIdx.x - e.row_begin);
   if (local < (long)e.rows_f) pw_weight_split_elem<1>(e.w, (int)e.Co, (int)e.Ci, 0, (int)(e.tm & 0xffffffffLL), e.wts_f, local * 256 + threadIdx.x);
   else pw_weight_split_elem<1>(e.w, (int)e.Co, (int)e.Ci, 1, (int)(e.tm >> 32), e.wts_b, (local - (long)e.rows_f) * 256 + threadIdx.x);
 }
@@ -136,75 +121,30 @@ __global__ __launch_bounds__(256) void pw_weight_split_f16_pair_kernel(const flo
 
 // ... of every registered 1x1 weight of a model in one launch (see conv3d_weight_split_f16_batch_kernel)
 __global__ __launch_bounds__(256) void pw_weight_split_f16_batch_kernel(const SplitEntry *__restrict__ tab, int n) {
-  const long long blk = blockIdx.x;
-  int i = 0;
-  while (i + 1 < n && tab[i + 1].row_begin <= blk) ++i;
-  const SplitEntry e = tab[i];
-  const int row = (int)(blk - e.row_begin);
+  const SplitEntry e = split_entry_of(tab, n, blockIdx.x);
+  const int row = (int)(blockIdx.x - e.row_begin);
   if (row < (int)e.rows_f) pw_weight_split_f16_row(e.w, (int)e.Co, (int)e.Ci, 0, (int)(e.tm & 0xffffffffLL), e.wts_f, e.wexp_f, row);
   else pw_weight_split_f16_row(e.w, (int)e.Co, (int)e.Ci, 1, (int)(e.tm >> 32), e.wts_b, e.wexp_b, row - (int)e.rows_f);
 }
 
-// ---- epilogue shared by the 1x1 GEMM kernels: D[i = m][j = point]; lanes = consecutive points (128-byte rows); bias; the optional
-// BatchNorm partial sums of (y - bias).  `lds` = the workgroup's staging buffer (>= 4 / WM * TM float pairs), free by now.
+// ---- epilogue of the 1x1 GEMM kernels: D[i = m][j = point]; lanes = consecutive points (128-byte rows of (B, M, N)); the rest is
+// gemm_tile_epilogue.  `lds` = the workgroup's staging buffer (>= 4 / WM * TM float pairs), free after the barrier.
 template <int NS, int MB, int WM>
 __device__ __forceinline__ void pb_epilogue(f32x16 (&acc)[MB / WM][2 * WM], uint32_t *lds, const float *__restrict__ bias,
                                             float *__restrict__ y, int M, int N, int b, int n0, int m0, int tile, int tiles_total,
                                             float2 *__restrict__ stats_part, const int *__restrict__ wexp, int x_shift) {
-  constexpr int TM = 32 * MB, MBW = MB / WM, NBW = 2 * WM;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, kh = lane >> 5;
-  const int wm = wave % WM, wn = wave / WM;
-  uint32_t *xs = lds;
-  const bool want_stats = stats_part != nullptr;
-  float2 *stat_lds = reinterpret_cast<float2 *>(xs);            // [4 / WM point groups][TM]
-  if (want_stats) __syncthreads();
-  float *yb = y + (size_t)b * M * N;
+  constexpr int NBW = 2 * WM;
+  const int wn = (threadIdx.x >> 6) / WM, j = threadIdx.x & 31;
+  int n[NBW];
+  bool nok[NBW];
 #pragma unroll
-  for (int mbl = 0; mbl < MBW; ++mbl) {
-    const int mb = wm * MBW + mbl;                              // row block inside the workgroup tile
-    float bv[16], unscale[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = m0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-      bv[r] = (bias != nullptr && m < M) ? bias[m] : 0.0f;
-      if constexpr (NS == 2) unscale[r] = exp2_int(-wexp[m]);   // wexp covers the padded rows of the tile
-    }
-    const float x_unscale = exp2_int(-x_shift);
-    float ss[16], qq[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ss[r] = qq[r] = 0.0f;
-#pragma unroll
-    for (int nb = 0; nb < NBW; ++nb) {
-      const int n = n0 + wn * (32 * NBW) + nb * 32 + j;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = m0 + mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        float v = acc[mbl][nb][r];
-        if constexpr (NS == 2) v = v * unscale[r] * x_unscale;  // powers of two: exact
-        if (want_stats) {                                       // statistics of (y - bias), see bn_finalize_kernel
-          const float mv = n < N ? v : 0.0f;
-          ss[r] += mv;
-          qq[r] += mv * mv;
-        }
-        v += bv[r];
-        if (n < N && m < M) yb[(size_t)m * N + n] = v;
-      }
-    }
-    if (want_stats) {
-      const float st = half_wave_sum16(ss, j), qt = half_wave_sum16(qq, j);
-      const int rr = (j >> 1) & 15;
-      if ((j & 1) == 0) stat_lds[wn * TM + mb * 32 + (rr & 3) + 8 * (rr >> 2) + 4 * kh] = make_float2(st, qt);
-    }
+  for (int nb = 0; nb < NBW; ++nb) {
+    n[nb] = n0 + wn * (32 * NBW) + nb * 32 + j;
+    nok[nb] = n[nb] < N;
   }
-  if (want_stats) {
-    __syncthreads();
-    if (tid < TM && m0 + tid < M) {
-      float2 t = stat_lds[tid];
-#pragma unroll
-      for (int w = 1; w < 4 / WM; ++w) { t.x += stat_lds[w * TM + tid].x; t.y += stat_lds[w * TM + tid].y; }
-      stats_part[(size_t)(m0 + tid) * tiles_total + tile] = t;
-    }
-  }
+  if (stats_part != nullptr) __syncthreads();
+  gemm_tile_epilogue<NS == 2, MB / WM, NBW, WM, 32 * MB>([&](int mbl, int nb, int r) { return acc[mbl][nb][r]; }, y + (size_t)b * M * N, N, n, nok, m0, M,
+                                                         bias, wexp, x_shift, stats_part, tiles_total, tile, reinterpret_cast<float2 *>(lds));
 }
 
 // f16x2 operand scale: amax_seg = 0 -> one scale for the whole tensor (x_absmax[0]); amax_seg = 256 -> x_absmax is an "amax buffer"
@@ -359,21 +299,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16_kernel(const float *__res
         bf[nb][s] = make_uint4(col[0], col[kPbN], col[2 * kPbN], col[3 * kPbN]);
       }
     __builtin_amdgcn_sched_barrier(0);
-#define PVCNN_PB_MFMA(SA, SB)                                                                                            \
-    _Pragma("unroll") for (int nb = 0; nb < NBW; ++nb)                                                                   \
-    _Pragma("unroll") for (int mb = 0; mb < MBW; ++mb)                                                                   \
-      acc[mb][nb] = mfma16<NS>(af[mb][SA], bf[nb][SB], acc[mb][nb])
-    if constexpr (NS == 1) {
-      PVCNN_PB_MFMA(0, 0);
-    } else if constexpr (NS == 2) {
-      PVCNN_PB_MFMA(1, 0); PVCNN_PB_MFMA(0, 1);                         // lo x hi, hi x lo, then hi x hi
-      PVCNN_PB_MFMA(0, 0);
-    } else {
-      PVCNN_PB_MFMA(2, 0); PVCNN_PB_MFMA(1, 1); PVCNN_PB_MFMA(0, 2);    // smallest partial products first
-      PVCNN_PB_MFMA(1, 0); PVCNN_PB_MFMA(0, 1);
-      PVCNN_PB_MFMA(0, 0);
-    }
-#undef PVCNN_PB_MFMA
+    split_products<NS>(acc, af, bf);
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (VEC) load_a(min(chunk + 1, chunks - 1));      // overwrites af once this chunk's MFMAs have been issued
     else if (chunk + 1 < chunks) load_a(chunk + 1);
@@ -502,20 +428,9 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f16_pipe_kernel(const float *_
           bf[nb][s] = make_uint4(lo.x, lo.y, hi.x, hi.y);
         }
       load_a(min(chunk + 1, chunks - 1), af_[d ^ 1]);
-      uint4 (&af)[MBW][NS] = af_[d];
       __builtin_amdgcn_sched_barrier(0);
       convert(va_[d ^ 1], vb_[d ^ 1], chunk + 1 < chunks ? x_scale : 0.0f, w);
-#define PVCNN_PB_MFMA(SA, SB)                                                                                            \
-      _Pragma("unroll") for (int nb = 0; nb < NBW; ++nb)                                                                 \
-      _Pragma("unroll") for (int mb = 0; mb < MBW; ++mb)                                                                 \
-        acc[mb][nb] = mfma16<NS>(af[mb][SA], bf[nb][SB], acc[mb][nb])
-      if constexpr (NS == 2) {
-        PVCNN_PB_MFMA(1, 0); PVCNN_PB_MFMA(0, 1);                       // lo x hi, hi x lo, then hi x hi
-        PVCNN_PB_MFMA(0, 0);
-      } else {
-        PVCNN_PB_MFMA(0, 0);
-      }
-#undef PVCNN_PB_MFMA
+      split_products<NS>(acc, af_[d], bf);
 #pragma unroll
       for (int i = 0; i < (NS == 2 ? 3 : 1) * MBW * NBW; ++i) {         // 1 MFMA, 2 (bf16: 4) vector-ALU; 24 (8) times
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
