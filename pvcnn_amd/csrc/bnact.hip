@@ -36,6 +36,9 @@ __device__ __forceinline__ void block_sum2(float &a, float &b, float *sm) {
   }
 }
 
+// four consecutive floats from a pointer that is only 4-byte aligned
+__device__ __forceinline__ float4 ld4_unaligned(const float *p) { return make_float4(p[0], p[1], p[2], p[3]); }
+
 // Variance as E[(x-K)^2] - E[x-K]^2 with a per-channel shift K close to the mean: the plain E[x^2] - E[x]^2 loses
 // all digits in fp32 partial sums once |mean| / std reaches ~1e3 (sum of squares rounded at 6e-8 * n * mean^2).
 // K = the channel's first element here; = the convolution's bias for the epilogue statistics (conv3d.hip, pointwise.hip).
@@ -49,13 +52,17 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_kernel(const float *__res
   if (sl == 0 && b == 0 && threadIdx.x == 0) shift[c] = K;
   const int lo = sl * kBnSlice, hi = min(S, lo + kBnSlice);
   float s = 0.f, q = 0.f;
+  // (the sums must not depend on where the row starts: a row of whole quads that is NOT on a 16-byte boundary -- a view at an odd
+  //  offset inside a larger buffer -- gives every thread the same four elements in the same order through four 4-byte loads)
+  auto quad = [&](float4 v) {
+    v.x -= K; v.y -= K; v.z -= K; v.w -= K;
+    s += (v.x + v.y) + (v.z + v.w);
+    q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+  };
   if ((S & 3) == 0 && aligned16(row)) {
-    for (int i = lo + threadIdx.x * 4; i < hi; i += kBnThreads * 4) {
-      float4 v = *reinterpret_cast<const float4 *>(row + i);
-      v.x -= K; v.y -= K; v.z -= K; v.w -= K;
-      s += (v.x + v.y) + (v.z + v.w);
-      q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-    }
+    for (int i = lo + threadIdx.x * 4; i < hi; i += kBnThreads * 4) quad(*reinterpret_cast<const float4 *>(row + i));
+  } else if ((S & 3) == 0) {
+    for (int i = lo + threadIdx.x * 4; i < hi; i += kBnThreads * 4) quad(ld4_unaligned(row + i));
   } else {
     for (int i = lo + threadIdx.x; i < hi; i += kBnThreads) { const float v = row[i] - K; s += v; q += v * v; }
   }
@@ -194,26 +201,31 @@ __global__ __launch_bounds__(kBnThreads) void bnact_bwd_reduce_kernel(const floa
   const size_t goff = (size_t)b * gy_bstride + (size_t)c * S;   // grad_y: channels of a cloud contiguous, clouds gy_bstride apart
   const int lo = sl * kBnSlice, hi = min(S, lo + kBnSlice);
   float s = 0.f, q = 0.f;
-  if ((S & 3) == 0 && aligned16(x + off) && (!gy || aligned16(gy + goff))) {
-    for (int i = lo + threadIdx.x * 4; i < hi; i += kBnThreads * 4) {
-      const float4 xv = *reinterpret_cast<const float4 *>(x + off + i);
-      const float4 gv = gy ? *reinterpret_cast<const float4 *>(gy + goff + i) : make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-      const float xs_[4] = {xv.x, xv.y, xv.z, xv.w};
-      float gs_[4] = {gv.x, gv.y, gv.z, gv.w};
-      if constexpr (DROP) {
-        float f[4];
-        drop_factors4(off + i, k0, k1, drop.thr, drop.scale, f);
+  // (as bn_stats_kernel: whole quads in the same order whether or not the two rows start on a 16-byte boundary)
+  auto quad = [&](int i, const float4 xv, const float4 gv) {
+    const float xs_[4] = {xv.x, xv.y, xv.z, xv.w};
+    float gs_[4] = {gv.x, gv.y, gv.z, gv.w};
+    if constexpr (DROP) {
+      float f[4];
+      drop_factors4(off + i, k0, k1, drop.thr, drop.scale, f);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) gs_[u] *= f[u];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float z = fmaf(xs_[u], scale, shift);
-        const float g = gs_[u] * (z > 0.f ? 1.0f : slope);
-        s += g;
-        q += g * ((xs_[u] - m) * r);
-      }
+      for (int u = 0; u < 4; ++u) gs_[u] *= f[u];
     }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float z = fmaf(xs_[u], scale, shift);
+      const float g = gs_[u] * (z > 0.f ? 1.0f : slope);
+      s += g;
+      q += g * ((xs_[u] - m) * r);
+    }
+  };
+  const float4 ones = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+  if ((S & 3) == 0 && aligned16(x + off) && (!gy || aligned16(gy + goff))) {
+    for (int i = lo + threadIdx.x * 4; i < hi; i += kBnThreads * 4)
+      quad(i, *reinterpret_cast<const float4 *>(x + off + i), gy ? *reinterpret_cast<const float4 *>(gy + goff + i) : ones);
+  } else if ((S & 3) == 0) {
+    for (int i = lo + threadIdx.x * 4; i < hi; i += kBnThreads * 4)
+      quad(i, ld4_unaligned(x + off + i), gy ? ld4_unaligned(gy + goff + i) : ones);
   } else {
     for (int i = lo + threadIdx.x; i < hi; i += kBnThreads) {
       const float xv = x[off + i];

@@ -13,6 +13,7 @@ Arithmetic modes (`nsplit`): 0 = fp32 MFMA, 1 = plain bf16 operands (autocast), 
 from typing import Callable, NamedTuple
 
 from . import _cache, _gradslots
+from ._align import aligned as _aligned
 
 
 class Product(NamedTuple):
@@ -69,7 +70,8 @@ PW = Product(
 def forward(p, be, ctx, given, weight, bias, want_stats, nsplit):
     """The forward of VoxelConv3d / PointwiseConv on backend `be`.  Both kinds look the amax tag up on `given`, the tensor object
     the caller handed over (the tag rides on the object: functional/_cache.py), not on its canonical view."""
-    x, w = p.canon(given.contiguous()), p.canon_w(weight.contiguous())
+    # (x on a 16-byte boundary: the vector-staging Conv3d launches and both f16x2 backward-weight kernels refuse any other pointer)
+    x, w = p.canon(_aligned(given)), p.canon_w(weight.contiguous())
     ctx.save_for_backward(x, w)
     ctx.has_bias, ctx.x_shape, ctx.w_shape = bias is not None, given.shape, weight.shape
     ctx.bias_param = bias                     # (only asked where its gradient should be written: _gradslots.claim)
@@ -107,7 +109,7 @@ def backward(p, be, ctx, received):
     x, w = ctx.saved_tensors
     if received is None:
         return None, None, None, None, None
-    grad_y = p.canon(received.contiguous())
+    grad_y = p.canon(_aligned(received))
     f16 = ctx.nsplit == 2
     # the f16x2 backward-weight kernel also serves the bf16 (autocast) mode: more accurate than bf16 operands and far faster than the
     # fp32-MFMA kernel (x_amax / g_amax are None there: the kernel's wrapper takes the global maxima in one read each)

@@ -19,6 +19,7 @@ import torch
 
 from ... import _lib
 from . import _cache
+from ._align import aligned as _aligned
 from ._product import CONV, PW
 
 __all__ = ['_backend']
@@ -564,6 +565,7 @@ class HipBackend:
     def absmax_bits(self, x):
         """One uint32 on the device: the bit pattern of max |x| (a 1-word amax buffer: the scalar scale of the f16x2 kernels)."""
         _f32(x, 'x')
+        x = _aligned(x)                      # (the kernel takes whole quads from a 16-byte boundary and refuses any other pointer)
         out = torch.empty((1,), dtype=torch.int32, device=x.device)
         _run(self.lib.pvcnn_absmax_bits, 'absmax_bits', x, x, x.numel(), out)
         return out
@@ -877,6 +879,7 @@ class HipBackend:
         """The apply pass of bnact_forward on known statistics, also emitting the row maxima of y: x (B,C,S) -> (y, winners (B,C) int64,
         values (B,C)) == (y, *y.max(dim=-1)[::-1]).  y_amax / row_keys: the views of amax_and_row_keys, ZEROED (bn_finalize)."""
         _f32(x, 'x')
+        x = _aligned(x)                      # (as absmax_bits: 16-byte loads only)
         b, c, s3 = x.shape
         _shape(s3 % 256 == 0 and amax_seg % 4 == 0 and 0 < amax_seg <= 256 and 256 % amax_seg == 0,
                'bnact_apply_rowmax: S % 256 == 0 and an amax_seg that is a multiple of 4 and divides 256 expected')

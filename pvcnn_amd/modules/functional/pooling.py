@@ -5,16 +5,10 @@ modules/pointnet.py:85), as one streaming pass forward and one backward (csrc/po
 import torch
 from torch.autograd import Function
 
+from ._align import aligned as _aligned
 from ._autograd import native, amp_fwd, amp_bwd
 
 __all__ = ['neighbor_max']
-
-
-def _aligned(t):
-    """contiguous AND on a 16-byte boundary (the kernels read rows with 16-byte loads): a contiguous view at an odd storage offset is
-    copied to a fresh allocation instead of being refused by the library."""
-    t = t.contiguous()
-    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 class NeighborMax(Function):
