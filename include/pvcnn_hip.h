@@ -338,6 +338,21 @@ PVCNN_API size_t pvcnn_absmax_tiles_count(int B, long L, int seg);      /* 1 + T
 PVCNN_API int pvcnn_absmax_tiles(const float *x, int B, int C, long L, int seg, void *out, void *ticket, void *stream);
 PVCNN_API int pvcnn_conv3d_fwd_split(const float *x, const void *wts, const float *bias, int B, int Ci, int Co, int R, int nsplit,
                            const void *x_absmax, int amax_seg /* 0 | R */, float *y, float *stats_part, void *stream);
+/* THE ACTIVATION TAIL (additions to ABI v17; inference with BatchNorm folded into the weights).  The four *_act entry points are
+ * their namesakes with two more steps behind the bias, in the products' epilogues:
+ *   y = v > 0 ? v : v * slope          (slope 0: ReLU; 0.1: PVConv's LeakyReLU)
+ *   y_amax != NULL: y's amax buffer is emitted.  y_amax points to 1 + (segments of y) words that the caller has ZEROED, y_amax_seg is
+ *   the segment length (R: one z row / 256 points); word [1 + t] receives the bits of max |y| over all channels of segment t, combined
+ *   across the row tiles by vector atomicMax on the bit patterns (order-independent).  Word [0] is not written: a table-only buffer,
+ *   like one made with PVCNN_TABLE_ONLY.  Same shape checks and the same arithmetic as the plain entry points:
+ *   y == leaky_relu(plain y, slope) bit for bit.  Same routes (pvcnn_*_fwd_split_route), with one exception: where the plain 1x1 launch
+ *   takes the persistent wide kernel (256 / 512 weight rows per item), pvcnn_pwconv_fwd_split_act takes the 128-row kernels, which
+ *   compute the same bits -- the wide kernel has no register left for the tail. */
+PVCNN_API int pvcnn_conv3d_fwd_split_act(const float *x, const void *wts, const float *bias, int B, int Ci, int Co, int R, int nsplit,
+                           const void *x_absmax, int amax_seg /* 0 | R */, float *y, float *stats_part, float slope, void *y_amax,
+                           int y_amax_seg /* R */, void *stream);
+PVCNN_API int pvcnn_conv3d_fwd_act(const float *x, const float *wt, const float *bias, int B, int Ci, int Co, int R, float *y,
+                           float slope, void *y_amax, int y_amax_seg /* R */, void *stream);
 
 /* Backward-weight in the same f16x2 arithmetic (csrc/conv3d_wgrad_f16.hip), R = 8, 12, 16 or 32 (workspace_bytes returns 0 for
  * any other R: use pvcnn_conv3d_bwd_weight).  x_absmax / gy_absmax: pvcnn_absmax_bits of x and grad_y (word [0] of an amax
@@ -385,6 +400,12 @@ PVCNN_API size_t pvcnn_pwconv_fwd_split_stats_parts(int B, int N);
 PVCNN_API int pvcnn_pwconv_fwd_split_route(int B, int K, int M, int N, int nsplit);
 PVCNN_API int pvcnn_pwconv_fwd_split(const float *x, const void *wts, const float *bias, int B, int K, int M, int N, int nsplit,
                            const void *x_absmax, int amax_seg /* 0 | 256 */, float *y, float *stats_part, void *stream);
+/* ... with the activation tail (see pvcnn_conv3d_fwd_split_act) */
+PVCNN_API int pvcnn_pwconv_fwd_split_act(const float *x, const void *wts, const float *bias, int B, int K, int M, int N, int nsplit,
+                           const void *x_absmax, int amax_seg /* 0 | 256 */, float *y, float *stats_part, float slope, void *y_amax,
+                           int y_amax_seg /* 256 */, void *stream);
+PVCNN_API int pvcnn_pwconv_fwd_act(const float *x, const float *wt, int wt_rows, const float *bias, int B, int K, int M, int N,
+                           float *y, float slope, void *y_amax, int y_amax_seg /* 256 */, void *stream);
 /* Backward-weight of the 1x1 convolution in f16x2 (csrc/pointwise_wgrad_f16.hip), N % 4 == 0 (workspace_bytes returns 0 otherwise:
  * use pvcnn_pwconv_bwd_weight).  x (B,K,N), grad_y (B,M,N) -> grad_w (M,K) [, grad_bias (M)]; *_absmax: pvcnn_absmax_bits of the two
  * tensors (word [0] of an amax buffer).  (ABI v12) x_amax_seg / gy_amax_seg > 0: the buffer is an amax buffer with segments of that

@@ -115,3 +115,37 @@ def adopt(model):
     if donor is not None:
         take(model, donor.forward)
     return model
+
+
+def fold_batchnorm(model):
+    """Opt-in, ONE line -- `model = pvcnn_amd.fold_batchnorm(model)` before handing a trained network to `evaluate.*`,
+    `rooms.segment_room` or the Frustum evaluation: puts `model` in eval() and folds every BatchNorm that directly follows a SharedMLP
+    1x1 convolution or a PVConv Conv3d (and is followed by a ReLU / LeakyReLU) into that convolution's weights.  Under
+    `torch.no_grad()` / `inference_mode` such a triple then runs as ONE product whose epilogue applies the activation and emits the
+    scale table of what it writes: no stand-alone BatchNorm pass, no re-read of the tensor (functional/_fold.py, functional/bnact.py:
+    run_layers).  The folded weights are snapshots attached to the convolutions as plain attributes: parameters, buffers and
+    `state_dict()` are untouched, checkpoints save and load as before.  A snapshot is never stale -- after any change to the six
+    tensors it was formed from (in place, by `load_state_dict`, by FlatAdam), `.train()`, or with gradients enabled, the modules run as
+    they always did; call `fold_batchnorm` again after changing the weights.  Returns `model`."""
+    import torch.nn as nn
+    from .modules.functional import _fold
+    from .modules.functional.bnact import _is_pointwise, _slope
+    model.eval()
+    for seq in model.modules():
+        if not isinstance(seq, nn.Sequential):
+            continue
+        kids = list(seq)
+        for conv, bn, act in zip(kids, kids[1:], kids[2:]):
+            if ((_is_pointwise(conv) or hasattr(conv, 'forward_with_stats')) and isinstance(bn, nn.modules.batchnorm._BatchNorm)
+                    and bn.running_mean is not None and bn.running_var is not None and bn.num_features == conv.out_channels
+                    and _slope(act) is not None):
+                _fold.attach(conv, bn)
+    return model
+
+
+def unfold_batchnorm(model):
+    """Remove the snapshots of `fold_batchnorm`: the model is the one it was before (its mode stays as it is).  Returns `model`."""
+    from .modules.functional import _fold
+    for m in model.modules():
+        _fold.detach(m)
+    return model

@@ -152,6 +152,11 @@ SIGNATURES = {
     'pvcnn_kitti_ap_match': (_i, [_vp] * 5 + [_ll, _ll, _ll, _i, _i] + [_vp] * 9 + [_i, _i, _i] + [_vp, _vp]),
     'pvcnn_kitti_ap_thresholds': (_i, [_vp, _ll, _vp, _i, _i, _vp, _vp, _vp]),
     'pvcnn_kitti_ap_workspace_bytes': (_sz, [_ll, _i]),
+    # the activation tail (folded inference): the namesakes' arguments + slope, y's amax buffer, its segment length
+    'pvcnn_conv3d_fwd_split_act': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _vp]),
+    'pvcnn_conv3d_fwd_act': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _f, _vp, _i, _vp]),
+    'pvcnn_pwconv_fwd_split_act': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _vp]),
+    'pvcnn_pwconv_fwd_act': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _f, _vp, _i, _vp]),
     'pvcnn_kitti_ap_stats': (_i, [_vp] * 5 + [_ll, _ll, _ll, _i, _i] + [_vp] * 9 + [_i, _i, _i] + [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
 }
 

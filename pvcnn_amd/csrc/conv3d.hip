@@ -109,11 +109,12 @@ __device__ __forceinline__ void stage_halo_tile(float *xs, const float *xb, int 
 
 // NBW = MFMA column blocks (32 voxels) per wave: 2 -> a 256-voxel workgroup tile, 1 -> a 128-voxel tile (twice
 // the workgroups: used when a 256-voxel grid would leave the chip with about one workgroup per CU).
-template <int TX, int TY, int TZ, int CIC, bool VEC, int NBW>
+// ACT: the activation tail of gemm_tile_epilogue (gemm_epilogue.h) behind the bias -- LeakyReLU(aa.slope) and y's amax table.
+template <int TX, int TY, int TZ, int CIC, bool VEC, int NBW, bool ACT = false>
 __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const float *__restrict__ x, const float *__restrict__ wt,
                                                            const float *__restrict__ bias, float *__restrict__ y,
                                                            int Ci, int Co, int R, int tiles_x, int tiles_y, int tiles_z,
-                                                           float2 *__restrict__ stats_part) {
+                                                           float2 *__restrict__ stats_part, ActArgs<ACT> aa) {
   static_assert(TX * TY * TZ == 128 * NBW, "a workgroup tile is 4 waves x NBW x 32 voxels");
   static_assert(CIC % 2 == 0, "channels are consumed in pairs (MFMA K = 2)");
   constexpr int HX = TX + 2, HY = TY + 2, HZ = TZ + 2, HS = HX * HY * HZ;
@@ -233,33 +234,41 @@ __global__ __launch_bounds__(256) void conv3d_igemm_kernel(const float *__restri
     asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(acc[mb][nb][r]));
     return v;
   };
-  gemm_tile_epilogue<false, 2, NBW, 1, kCoTile>(acc_at, y + (size_t)b * Co * S, S, voff, vok, co0, Co, bias, nullptr, 0, stats_part, gridDim.x,
-                                                blockIdx.x, reinterpret_cast<float2 *>(lds));
+  if constexpr (ACT) {
+    static_assert(TX * TY <= 256, "one thread per z row of the tile");
+    const auto tail = act_amax_tail(aa.slope, aa.amax, TX * TY, [](int nb) { return (int)((threadIdx.x >> 6) * 32 * NBW + nb * 32 + (threadIdx.x & 31)) / TZ; },
+                                    ZRowIndex<TY>{b, R, x0, y0});
+    gemm_tile_epilogue<false, 2, NBW, 1, kCoTile>(acc_at, y + (size_t)b * Co * S, S, voff, vok, co0, Co, bias, nullptr, 0, stats_part, gridDim.x,
+                                                  blockIdx.x, reinterpret_cast<float2 *>(lds), tail);
+  } else {
+    gemm_tile_epilogue<false, 2, NBW, 1, kCoTile>(acc_at, y + (size_t)b * Co * S, S, voff, vok, co0, Co, bias, nullptr, 0, stats_part, gridDim.x,
+                                                  blockIdx.x, reinterpret_cast<float2 *>(lds));
+  }
 }
 
-template <int TX, int TY, int TZ, int CIC, bool VEC, int NBW>
+template <int TX, int TY, int TZ, int CIC, bool VEC, int NBW, bool ACT>
 static int launch_igemm_v(const float *x, const float *wt, const float *bias, float *y, int B, int Ci, int Co, int R,
-                          hipStream_t s, float2 *stats_part) {
+                          hipStream_t s, float2 *stats_part, ActArgs<ACT> aa) {
   constexpr int HS = (TX + 2) * (TY + 2) * (TZ + 2);
   const size_t lds = (size_t)(CIC * HS + CIC * 27 * kCoTile) * sizeof(float);
   const int tx = ceil_div(R, TX), ty = ceil_div(R, TY), tz = ceil_div(R, TZ);
-  auto k = conv3d_igemm_kernel<TX, TY, TZ, CIC, VEC, NBW>;
+  auto k = conv3d_igemm_kernel<TX, TY, TZ, CIC, VEC, NBW, ACT>;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { set_error("conv3d: LDS attribute: %s", hipGetErrorString(e)); return (int)e; }
   }
   hipLaunchKernelGGL(k, dim3((unsigned)((long)B * tx * ty * tz), ceil_div(Co, kCoTile)), dim3(256), lds, s, x, wt, bias,
-                     y, Ci, Co, R, tx, ty, tz, stats_part);
+                     y, Ci, Co, R, tx, ty, tz, stats_part, aa);
   return check_launch("conv3d_igemm");
 }
 
-template <int TX, int TY, int TZ, int CIC, int NBW = 2>
+template <int TX, int TY, int TZ, int CIC, int NBW = 2, bool ACT = false>
 static int launch_igemm(const float *x, const float *wt, const float *bias, float *y, int B, int Ci, int Co, int R,
-                        hipStream_t s, float2 *stats_part) {
+                        hipStream_t s, float2 *stats_part, ActArgs<ACT> aa = {}) {
   // vector staging needs full aligned z-rows (R == TZ) and 16-byte aligned weight rows (whole quads of co)
   const bool vec = (R == TZ) && (Co % 4 == 0) && aligned16(x) && aligned16(wt);
-  return vec ? launch_igemm_v<TX, TY, TZ, CIC, true, NBW>(x, wt, bias, y, B, Ci, Co, R, s, stats_part)
-             : launch_igemm_v<TX, TY, TZ, CIC, false, NBW>(x, wt, bias, y, B, Ci, Co, R, s, stats_part);
+  return vec ? launch_igemm_v<TX, TY, TZ, CIC, true, NBW, ACT>(x, wt, bias, y, B, Ci, Co, R, s, stats_part, aa)
+             : launch_igemm_v<TX, TY, TZ, CIC, false, NBW, ACT>(x, wt, bias, y, B, Ci, Co, R, s, stats_part, aa);
 }
 
 
@@ -667,15 +676,16 @@ static int igemm_variant(int B, int Co, int R, long *nparts) {
   return v;
 }
 
+template <bool ACT = false>
 static int conv3d_fwd_impl(const float *x, const float *wt, const float *bias, int B, int Ci, int Co, int R, float *y,
-                           float2 *stats_part, hipStream_t s) {
+                           float2 *stats_part, hipStream_t s, ActArgs<ACT> aa = {}) {
   long nparts;
   switch (igemm_variant(B, Co, R, &nparts)) {
-    case 0: return launch_igemm<2, 4, 32, 4>(x, wt, bias, y, B, Ci, Co, R, s, stats_part);
-    case 1: return launch_igemm<2, 4, 16, 4, 1>(x, wt, bias, y, B, Ci, Co, R, s, stats_part);
-    case 2: return launch_igemm<4, 4, 16, 4>(x, wt, bias, y, B, Ci, Co, R, s, stats_part);
-    case 4: return launch_igemm<2, 8, 8, 4, 1>(x, wt, bias, y, B, Ci, Co, R, s, stats_part);
-    default: return launch_igemm<4, 8, 8, 4>(x, wt, bias, y, B, Ci, Co, R, s, stats_part);
+    case 0: return launch_igemm<2, 4, 32, 4, 2, ACT>(x, wt, bias, y, B, Ci, Co, R, s, stats_part, aa);
+    case 1: return launch_igemm<2, 4, 16, 4, 1, ACT>(x, wt, bias, y, B, Ci, Co, R, s, stats_part, aa);
+    case 2: return launch_igemm<4, 4, 16, 4, 2, ACT>(x, wt, bias, y, B, Ci, Co, R, s, stats_part, aa);
+    case 4: return launch_igemm<2, 8, 8, 4, 1, ACT>(x, wt, bias, y, B, Ci, Co, R, s, stats_part, aa);
+    default: return launch_igemm<4, 8, 8, 4, 2, ACT>(x, wt, bias, y, B, Ci, Co, R, s, stats_part, aa);
   }
 }
 
@@ -686,6 +696,18 @@ extern "C" int pvcnn_conv3d_fwd(const float *x, const float *wt, const float *bi
   PVCNN_REQUIRE(x && wt && y, "null pointer");
   PVCNN_REQUIRE((long)R * R * R * (long)std::max(Ci, Co) <= 0x7fffffffL, "grid too large");
   return conv3d_fwd_impl(x, wt, bias, B, Ci, Co, R, y, nullptr, static_cast<hipStream_t>(stream));
+}
+
+// pvcnn_conv3d_fwd with the activation tail (include/pvcnn_hip.h): y = LeakyReLU(conv3d(x, w) + bias, slope), y's amax table emitted
+extern "C" int pvcnn_conv3d_fwd_act(const float *x, const float *wt, const float *bias, int B, int Ci, int Co, int R, float *y,
+                                    float slope, void *y_amax, int y_amax_seg, void *stream) {
+  PVCNN_REQUIRE(B >= 0 && Ci > 0 && Co > 0 && R > 0, "bad size");
+  PVCNN_REQUIRE(!y_amax || y_amax_seg == R, "y_amax_seg must be R (one maximum per z row)");
+  if (B == 0) return 0;
+  PVCNN_REQUIRE(x && wt && y, "null pointer");
+  PVCNN_REQUIRE((long)R * R * R * (long)std::max(Ci, Co) <= 0x7fffffffL, "grid too large");
+  return conv3d_fwd_impl<true>(x, wt, bias, B, Ci, Co, R, y, nullptr, static_cast<hipStream_t>(stream),
+                               ActArgs<true>{slope, static_cast<uint32_t *>(y_amax)});
 }
 
 extern "C" size_t pvcnn_conv3d_fwd_stats_parts(int B, int Co, int R) {

@@ -306,16 +306,41 @@ __device__ __attribute__((noinline)) void write_zero_input_tile(float *__restric
   if (stats_part != nullptr && tid < rows) stats_part[(size_t)(co0 + tid) * gridDim.x + blockIdx.x] = make_float2(0.0f, 0.0f);
 }
 
+// ... with the activation tail (gemm_epilogue.h): every output of row r is act(bias[r]), and every z row of the tile inside the grid
+// has the maximum over the tile's rows of |act(bias[r])| -- one atomicMax per z row, like the full path's.
+template <int TX, int TY, int TZ>
+__device__ __attribute__((noinline)) void write_zero_input_tile_act(float *__restrict__ yb, const float *__restrict__ bias, int Co, int co0, int R,
+                                                          int b, int x0, int y0, int z0, float2 *__restrict__ stats_part, int tid,
+                                                          float slope, uint32_t *__restrict__ amax) {
+  const size_t RR = (size_t)R * R, S = RR * R;
+  const int rows = min(kCoTileB, Co - co0);
+  const int items = rows * TX * TY * TZ;
+  for (int e = tid; e < items; e += 256) {
+    const int zt = e % TZ, yt = (e / TZ) % TY, xt = (e / (TZ * TY)) % TX, r = e / (TZ * TY * TX);
+    const int gx = x0 + xt, gy = y0 + yt, gz = z0 + zt;
+    if (gx < R && gy < R && gz < R)
+      yb[(size_t)(co0 + r) * S + (size_t)gx * RR + (size_t)gy * R + gz] = act_tail(0.0f + (bias != nullptr ? bias[co0 + r] : 0.0f), slope);
+  }
+  if (stats_part != nullptr && tid < rows) stats_part[(size_t)(co0 + tid) * gridDim.x + blockIdx.x] = make_float2(0.0f, 0.0f);
+  if (amax != nullptr && bias != nullptr && tid < TX * TY && z0 < R) {
+    const long t = ZRowIndex<TY>{b, R, x0, y0}(tid);
+    uint32_t m = 0u;
+    for (int r = 0; r < rows; ++r) m = max(m, act_abs_bits(act_tail(0.0f + bias[co0 + r], slope)));
+    if (t >= 0 && m != 0u) atomicMax(amax + 1 + t, m);
+  }
+}
+
 // f16x2 operand scale: amax_seg = 0 -> one scale for the whole tensor (x_absmax[0]); amax_seg = R -> x_absmax is an "amax buffer"
 // (include/pvcnn_hip.h) with one maximum per z row (b, gx, gy) behind the global one, and the workgroup scales ITS halo tile by the
 // largest row it stages: an outlier somewhere in the grid costs precision only in the tiles that contain it.
-template <int NS, int TX, int TY, int TZ, bool VEC, bool CO32 = false>
+// ACT: the activation tail of gemm_tile_epilogue (gemm_epilogue.h) behind the bias -- LeakyReLU(aa.slope) and y's amax table.
+template <int NS, int TX, int TY, int TZ, bool VEC, bool CO32 = false, bool ACT = false>
 __global__ __launch_bounds__(256, (NS == 3 || TX * TY * TZ == 512 || TZ <= 16) ? 2 : 3) void conv3d_igemm_bf16_kernel(const float *__restrict__ x, const uint16_t *__restrict__ wts,
                                                                    const float *__restrict__ bias, float *__restrict__ y,
                                                                    int Ci, int Co, int R, int tiles_x, int tiles_y, int tiles_z,
                                                                    float2 *__restrict__ stats_part,
                                                                    const uint32_t *__restrict__ x_absmax, const int *__restrict__ wexp,
-                                                                   int amax_seg) {
+                                                                   int amax_seg, ActArgs<ACT> aa) {
   static_assert(TX * TY * TZ == 64 || TX * TY * TZ == 128 || TX * TY * TZ == 256 || TX * TY * TZ == 512, "a workgroup tile is 4 waves x NBW x 32 voxels");
   constexpr int HX = TX + 2, HY = TY + 2, HZ = TZ + 2, HS = HX * HY * HZ;
   // Wave arrangement inside the 64-channel x (TX*TY*TZ)-voxel workgroup tile.  Every lane fetches its own A (weight) fragments from
@@ -365,7 +390,8 @@ __global__ __launch_bounds__(256, (NS == 3 || TX * TY * TZ == 512 || TZ <= 16) ?
       tm = *x_absmax;
     }
     if (tm == 0u) {                                             // (uniform: every thread of the workgroup leaves before the first barrier)
-      write_zero_input_tile<TX, TY, TZ>(y + (size_t)b * Co * S, bias, Co, co0, R, x0, y0, z0, stats_part, tid);
+      if constexpr (ACT) write_zero_input_tile_act<TX, TY, TZ>(y + (size_t)b * Co * S, bias, Co, co0, R, b, x0, y0, z0, stats_part, tid, aa.slope, aa.amax);
+      else write_zero_input_tile<TX, TY, TZ>(y + (size_t)b * Co * S, bias, Co, co0, R, x0, y0, z0, stats_part, tid);
       return;
     }
     x_shift = scale_shift(tm);
@@ -539,8 +565,17 @@ __global__ __launch_bounds__(256, (NS == 3 || TX * TY * TZ == 512 || TZ <= 16) ?
     vok[nb] = gx < R && gy < R && gz < R;
     voff[nb] = (size_t)gx * RR + (size_t)gy * R + gz;
   }
-  gemm_tile_epilogue<NS == 2, MBW, NBW, WM, kCoTileB>([&](int mbl, int nb, int r) { return acc[mbl][nb][r]; }, yb, S, voff, vok, co0, Co, bias, wexp,
-                                                      x_shift, stats_part, gridDim.x, blockIdx.x, reinterpret_cast<float2 *>(lds_u));
+  if constexpr (ACT) {
+    static_assert(TX * TY <= 256, "one thread per z row of the tile");
+    const auto tail = act_amax_tail(aa.slope, aa.amax, TX * TY,
+                                    [](int nb) { return (int)(((threadIdx.x >> 6) / WM) * (32 * NBW) + nb * 32 + (threadIdx.x & 31)) / TZ; },
+                                    ZRowIndex<TY>{b, R, x0, y0});
+    gemm_tile_epilogue<NS == 2, MBW, NBW, WM, kCoTileB>([&](int mbl, int nb, int r) { return acc[mbl][nb][r]; }, yb, S, voff, vok, co0, Co, bias, wexp,
+                                                        x_shift, stats_part, gridDim.x, blockIdx.x, reinterpret_cast<float2 *>(lds_u), tail);
+  } else {
+    gemm_tile_epilogue<NS == 2, MBW, NBW, WM, kCoTileB>([&](int mbl, int nb, int r) { return acc[mbl][nb][r]; }, yb, S, voff, vok, co0, Co, bias, wexp,
+                                                        x_shift, stats_part, gridDim.x, blockIdx.x, reinterpret_cast<float2 *>(lds_u));
+  }
 }
 
 // ---- the 128-voxel f16x2 tile (TX x TY x 16, R = 16 grids), pipelined ----------------------------------------------------------
@@ -561,12 +596,12 @@ __global__ __launch_bounds__(256, (NS == 3 || TX * TY * TZ == 512 || TZ <= 16) ?
 //     Ci % 16 == 0 is required, other layers stay on conv3d_igemm_bf16_kernel), so the compiler's vmcnt waits leave the younger
 //     loads in flight; weights and rows are addressed as uniform base + one 32-bit lane offset, LDS fragments as lane base + immediate.
 // Same products in the same order per output element as conv3d_igemm_bf16_kernel<2, TX, TY, 16, true>.
-template <int TX, int TY>
+template <int TX, int TY, bool ACT = false>
 __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const float *__restrict__ x, const uint16_t *__restrict__ wts,
                                                                        const float *__restrict__ bias, float *__restrict__ y, int Ci, int Co,
                                                                        int R, int tiles_x, int tiles_y, float2 *__restrict__ stats_part,
                                                                        const uint32_t *__restrict__ x_absmax, const int *__restrict__ wexp,
-                                                                       int amax_seg) {
+                                                                       int amax_seg, ActArgs<ACT> aa) {
   constexpr int NS = 2, TZ = 16, HX = TX + 2, HY = TY + 2, HZ = TZ + 2, HS = HX * HY * HZ, TILE = NS * HS * 8;
   static_assert(TX * TY * TZ == 128, "4 waves, 2 x 2: 32 channels x 64 voxels each");
   constexpr int NBW = 2, WBLK = 3 * NS * kCoTileB * kKc;
@@ -600,7 +635,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const flo
     tm = *x_absmax;
   }
   if (tm == 0u) {                                               // zero-input tile: see write_zero_input_tile
-    write_zero_input_tile<TX, TY, TZ>(y + (size_t)b * Co * S, bias, Co, co0, R, x0, y0, 0, stats_part, tid);
+    if constexpr (ACT) write_zero_input_tile_act<TX, TY, TZ>(y + (size_t)b * Co * S, bias, Co, co0, R, b, x0, y0, 0, stats_part, tid, aa.slope, aa.amax);
+    else write_zero_input_tile<TX, TY, TZ>(y + (size_t)b * Co * S, bias, Co, co0, R, x0, y0, 0, stats_part, tid);
     return;
   }
   const int x_shift = scale_shift(tm);
@@ -721,8 +757,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const flo
     vok[nb] = ox < R && oy < R && zt < R;
     voff[nb] = (size_t)ox * RR + (size_t)oy * R + zt;
   }
-  gemm_tile_epilogue<true, 1, NBW, 2, kCoTileB>([&](int, int nb, int r) { return acc[0][nb][r]; }, yb, S, voff, vok, co0, Co, bias, wexp, x_shift,
-                                                stats_part, gridDim.x, blockIdx.x, reinterpret_cast<float2 *>(lds_u));
+  if constexpr (ACT) {
+    const auto tail = act_amax_tail(aa.slope, aa.amax, TX * TY, [wn, jj](int nb) { return (wn * (32 * NBW) + nb * 32 + jj) / TZ; }, ZRowIndex<TY>{b, R, x0, y0});
+    gemm_tile_epilogue<true, 1, NBW, 2, kCoTileB>([&](int, int nb, int r) { return acc[0][nb][r]; }, yb, S, voff, vok, co0, Co, bias, wexp, x_shift,
+                                                  stats_part, gridDim.x, blockIdx.x, reinterpret_cast<float2 *>(lds_u), tail);
+  } else {
+    gemm_tile_epilogue<true, 1, NBW, 2, kCoTileB>([&](int, int nb, int r) { return acc[0][nb][r]; }, yb, S, voff, vok, co0, Co, bias, wexp, x_shift,
+                                                  stats_part, gridDim.x, blockIdx.x, reinterpret_cast<float2 *>(lds_u));
+  }
 }
 
 // ---- the 512-voxel f16x2 tile of the R = 32 grids, ONE workgroup per CU, persistent (round 6) -----------------------------------
@@ -753,12 +795,15 @@ template <int TZ> struct CwGeom {
   static constexpr size_t LDS = (size_t)2 * TILEB + (size_t)4 * kCoTileB * sizeof(float2);
 };
 
-template <int TZ, int AB = 0>
+// ACT: the activation tail (the contract stated at gemm_tile_epilogue, in this kernel's own text): LeakyReLU(aa.slope) behind the bias;
+// a wave owns whole z rows, so their maxima meet in the wave's registers and one lane issues one atomicMax per z row.
+template <int TZ, int AB = 0, bool ACT = false>
 __global__ __launch_bounds__(256, 1) void conv3d_igemm_f16_wide_kernel(const float *__restrict__ x, const uint16_t *__restrict__ wts,
                                                                        const float *__restrict__ bias, float *__restrict__ y, int Ci, int Co,
                                                                        int B, float2 *__restrict__ stats_part,
                                                                        const uint32_t *__restrict__ x_absmax, const int *__restrict__ wexp,
-                                                                       int amax_seg, unsigned x_bytes, unsigned w_bytes, int stats_parts) {
+                                                                       int amax_seg, unsigned x_bytes, unsigned w_bytes, int stats_parts,
+                                                                       ActArgs<ACT> aa) {
   static_assert(TZ == 32 || TZ == 16, "the tile spans z: R = 32 or 16");
   using G = CwGeom<TZ>;
   constexpr int NS = 2, R = TZ, TX = 4, TY = 4, HX = G::HX, HY = G::HY, HZ = G::HZ, HS = G::HS, NBW = TZ / 8, MBW = 2;
@@ -1047,6 +1092,11 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_f16_wide_kernel(const flo
       // the lane's byte offset of (co0 + 4 kh, x0 + wave, y0 + its row in the block, its z); row q of block mb: + (mb * 32 + rowq) * S * 4;
       // column block nb: + RPB * nb * R * 4
       const uint32_t yoff = (uint32_t)((co0 + 4 * khe) * S + (cur.x0 + wave) * RR + (cur.y0 + vrow_e) * R + vz_e) * 4u;
+      [[maybe_unused]] uint32_t am[NBW];
+      if constexpr (ACT) {
+#pragma unroll
+        for (int nb = 0; nb < NBW; ++nb) am[nb] = 0u;
+      }
 #pragma unroll
       for (int mb = 0; mb < MBW; ++mb)
 #pragma unroll
@@ -1070,6 +1120,10 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_f16_wide_kernel(const flo
                 qq[qi] += v * v;
               }
               v += bv[qi];
+              if constexpr (ACT) {
+                v = act_tail(v, aa.slope);
+                if (co0 + mb * 32 + (q & 3) + 8 * (q >> 2) + 4 * khe < Co) am[nb] = max(am[nb], act_abs_bits(v));
+              }
               // (rows >= Co of the last channel block: beyond the descriptor, dropped)
               __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), yrsrc,
                                                     yoff + (uint32_t)((mb * 32 + (q & 3) + 8 * (q >> 2)) * (S * 4)) + (uint32_t)(RPB * nb * R * 4), 0, 0);
@@ -1081,6 +1135,17 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_f16_wide_kernel(const flo
           }
           __builtin_amdgcn_sched_barrier(0);
         }
+      if constexpr (ACT) {
+        if (aa.amax != nullptr) {                               // z row (b, x0 + wave, y0 + RPB nb + vr): the lanes with vrow == vr of block nb
+#pragma unroll
+          for (int nb = 0; nb < NBW; ++nb)
+#pragma unroll
+            for (int vr = 0; vr < RPB; ++vr) {
+              const uint32_t m = wave_max_u32((RPB == 1 || vrow_e == vr) ? am[nb] : 0u);
+              if ((tid_e & 63) == 0 && m != 0u) atomicMax(aa.amax + 1 + ((size_t)cur.b * R + cur.x0 + wave) * R + cur.y0 + RPB * nb + vr, m);
+            }
+        }
+      }
       if (want_stats) {
         lds_barrier();
         if (tid_e < kCoTileB && co0 + tid_e < Co) {
@@ -1101,31 +1166,31 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_f16_wide_kernel(const flo
 
 static_assert(route::kNumCU == kNumCU && route::kCoTileB == kCoTileB && route::kKc == kKc, "route.h plans with this file's constants");
 
-template <int TX, int TY>
+template <int TX, int TY, bool ACT = false>
 static int launch_igemm_f16_pipe(const float *x, const uint16_t *wts, const float *bias, float *y, int B, int Ci, int Co, int R, hipStream_t s,
-                                 float2 *stats_part, const uint32_t *x_absmax, const int *wexp, int amax_seg) {
+                                 float2 *stats_part, const uint32_t *x_absmax, const int *wexp, int amax_seg, ActArgs<ACT> aa = {}) {
   constexpr int HS = (TX + 2) * (TY + 2) * 18;
   const size_t lds = (size_t)2 * 2 * HS * 8 * sizeof(uint32_t);                  // two tiles of two planes
   const int tx = ceil_div(R, TX), ty = ceil_div(R, TY);
-  hipLaunchKernelGGL((conv3d_igemm_f16_pipe_kernel<TX, TY>), dim3((unsigned)((long)B * tx * ty), ceil_div(Co, kCoTileB)), dim3(256), lds, s, x,
-                     wts, bias, y, Ci, Co, R, tx, ty, stats_part, x_absmax, wexp, amax_seg);
+  hipLaunchKernelGGL((conv3d_igemm_f16_pipe_kernel<TX, TY, ACT>), dim3((unsigned)((long)B * tx * ty), ceil_div(Co, kCoTileB)), dim3(256), lds, s, x,
+                     wts, bias, y, Ci, Co, R, tx, ty, stats_part, x_absmax, wexp, amax_seg, aa);
   return check_launch("conv3d_igemm_f16_pipe");
 }
 
-template <int NS, int TX, int TY, int TZ, bool VEC, bool CO32 = false>
+template <int NS, int TX, int TY, int TZ, bool VEC, bool CO32 = false, bool ACT = false>
 static int launch_igemm_bf16(const float *x, const uint16_t *wts, const float *bias, float *y, int B, int Ci, int Co, int R,
                              hipStream_t s, float2 *stats_part, const uint32_t *x_absmax = nullptr, const int *wexp = nullptr,
-                             int amax_seg = 0) {
+                             int amax_seg = 0, ActArgs<ACT> aa = {}) {
   constexpr int HS = (TX + 2) * (TY + 2) * (TZ + 2);
   const size_t lds = std::max((size_t)NS * HS * 8 * sizeof(uint32_t), (size_t)4 * kCoTileB * sizeof(float2));
   const int tx = ceil_div(R, TX), ty = ceil_div(R, TY), tz = ceil_div(R, TZ);
-  auto k = conv3d_igemm_bf16_kernel<NS, TX, TY, TZ, VEC, CO32>;
+  auto k = conv3d_igemm_bf16_kernel<NS, TX, TY, TZ, VEC, CO32, ACT>;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) { set_error("conv3d(bf16): LDS attribute: %s", hipGetErrorString(e)); return (int)e; }
   }
   hipLaunchKernelGGL(k, dim3((unsigned)((long)B * tx * ty * tz), ceil_div(Co, kCoTileB)), dim3(256), lds, s, x, wts, bias, y,
-                     Ci, Co, R, tx, ty, tz, stats_part, x_absmax, wexp, amax_seg);
+                     Ci, Co, R, tx, ty, tz, stats_part, x_absmax, wexp, amax_seg, aa);
   return check_launch("conv3d_igemm_bf16");
 }
 
@@ -1288,8 +1353,9 @@ extern "C" int pvcnn_conv3d_fwd_split_route(int B, int Ci, int Co, int R, int ns
 
 // y = conv3d(x, w) + bias with the pre-split weights of pvcnn_conv3d_weight_split (forward layout: Ci, Co as given; backward-data:
 // call with x = grad_y, Ci = the forward Co, Co = the forward Ci, bias = NULL and the for_bwd_data = 1 weights).
+template <bool ACT = false>
 static int conv3d_fwd_split_impl(const float *x, const void *wts, const float *bias, int B, int Ci, int Co, int R, int nsplit,
-                                 const void *x_absmax, int amax_seg, float *y, float *stats_part, void *stream) {
+                                 const void *x_absmax, int amax_seg, float *y, float *stats_part, void *stream, ActArgs<ACT> aa = {}) {
   PVCNN_REQUIRE(B >= 0 && Ci > 0 && Co > 0 && R > 0, "bad size");
   PVCNN_REQUIRE(nsplit >= 1 && nsplit <= 3, "nsplit must be 1 (bf16), 2 (f16x2) or 3 (bf16x3)");
   PVCNN_REQUIRE(nsplit != 2 || x_absmax, "f16x2 needs the input's pvcnn_absmax_bits / pvcnn_absmax_tiles");
@@ -1305,7 +1371,7 @@ static int conv3d_fwd_split_impl(const float *x, const void *wts, const float *b
   PVCNN_REQUIRE(!p.vec || aligned16(x), "x must be 16-byte aligned");
   const uint32_t *am = static_cast<const uint32_t *>(x_absmax);
   const int *wexp = nsplit == 2 ? reinterpret_cast<const int *>(static_cast<const char *>(wts) + weight_image_bytes(Ci, Co, 2)) : nullptr;
-#define PVCNN_IGEMM(NS, TX, TY, TZ, VEC) launch_igemm_bf16<NS, TX, TY, TZ, VEC>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg)
+#define PVCNN_IGEMM(NS, TX, TY, TZ, VEC) launch_igemm_bf16<NS, TX, TY, TZ, VEC, false, ACT>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg, aa)
 #define PVCNN_IGEMM_NS(TX, TY, TZ, VEC) (nsplit == 3 ? PVCNN_IGEMM(3, TX, TY, TZ, VEC) : nsplit == 2 ? PVCNN_IGEMM(2, TX, TY, TZ, VEC) : PVCNN_IGEMM(1, TX, TY, TZ, VEC))
 #define PVCNN_IGEMM_VEC(TX, TY, TZ) (p.vec ? PVCNN_IGEMM_NS(TX, TY, TZ, true) : PVCNN_IGEMM_NS(TX, TY, TZ, false))
   switch (p.kernel) {
@@ -1313,12 +1379,12 @@ static int conv3d_fwd_split_impl(const float *x, const void *wts, const float *b
       const unsigned xb = (unsigned)((size_t)B * Ci * R * R * R * 4), wb = (unsigned)weight_image_bytes(Ci, Co, 2);
 #define PVCNN_CW_LAUNCH(TZV, ABV)                                                                                                    \
       do {                                                                                                                             \
-        auto kw = conv3d_igemm_f16_wide_kernel<TZV, ABV>;                                                                              \
+        auto kw = conv3d_igemm_f16_wide_kernel<TZV, ABV, ACT>;                                                                            \
         const int lds_bytes = (int)CwGeom<TZV>::LDS;                                                                                   \
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kw), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes); \
         if (e != hipSuccess) { set_error("conv3d(wide): LDS attribute: %s", hipGetErrorString(e)); return (int)e; }                    \
         hipLaunchKernelGGL(kw, dim3(p.grid_x), dim3(256), lds_bytes, s, x, w16, bias, y, Ci, Co, B, sp, am, wexp, amax_seg, xb, wb,    \
-                           (int)p.stats_slots);                                                                                        \
+                           (int)p.stats_slots, aa);                                                                                     \
       } while (0)
 #ifdef PVCNN_ABLATE
       const char *ab_env = getenv("PVCNN_CONV_ABLATE");
@@ -1346,10 +1412,10 @@ static int conv3d_fwd_split_impl(const float *x, const void *wts, const float *b
       return check_launch("conv3d_igemm_f16_wide");
     }
     case route::ConvKernel::Pipe:
-      return launch_igemm_f16_pipe<2, 4>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg);
+      return launch_igemm_f16_pipe<2, 4, ACT>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg, aa);
     case route::ConvKernel::IgemmCo32:
-      return p.tx == 4 ? launch_igemm_bf16<2, 4, 4, 32, true, true>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg)
-                       : launch_igemm_bf16<2, 2, 4, 32, true, true>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg);
+      return p.tx == 4 ? launch_igemm_bf16<2, 4, 4, 32, true, true, ACT>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg, aa)
+                       : launch_igemm_bf16<2, 2, 4, 32, true, true, ACT>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg, aa);
     case route::ConvKernel::Igemm:
       break;
   }
@@ -1365,4 +1431,14 @@ static int conv3d_fwd_split_impl(const float *x, const void *wts, const float *b
 extern "C" int pvcnn_conv3d_fwd_split(const float *x, const void *wts, const float *bias, int B, int Ci, int Co, int R, int nsplit,
                                       const void *x_absmax, int amax_seg, float *y, float *stats_part, void *stream) {
   return conv3d_fwd_split_impl(x, wts, bias, B, Ci, Co, R, nsplit, x_absmax, amax_seg, y, stats_part, stream);
+}
+
+// pvcnn_conv3d_fwd_split with the activation tail (include/pvcnn_hip.h): y = LeakyReLU(conv3d(x, w) + bias, slope); y_amax: NULL or y's
+// zeroed amax buffer, whose table the epilogues fill (y_amax_seg = R)
+extern "C" int pvcnn_conv3d_fwd_split_act(const float *x, const void *wts, const float *bias, int B, int Ci, int Co, int R, int nsplit,
+                                          const void *x_absmax, int amax_seg, float *y, float *stats_part, float slope, void *y_amax,
+                                          int y_amax_seg, void *stream) {
+  PVCNN_REQUIRE(!y_amax || y_amax_seg == R, "y_amax_seg must be R (one maximum per z row)");
+  return conv3d_fwd_split_impl<true>(x, wts, bias, B, Ci, Co, R, nsplit, x_absmax, amax_seg, y, stats_part, stream,
+                                     ActArgs<true>{slope, static_cast<uint32_t *>(y_amax)});
 }

@@ -4,6 +4,7 @@
 #pragma once
 #include "common.h"
 #include "split16.h"
+#include <type_traits>
 
 namespace pvcnn {
 
@@ -24,11 +25,66 @@ namespace pvcnn {
 //   * one float2 (sum, sum of squares) per row < row_limit: stats_part[row * stats_stride + stats_slot], written by exactly one
 //     workgroup -- the partials are combined by bn_finalize in fp64.
 // stat_lds: (4 / WM) * ROWS float pairs of LDS that no wave reads any more (the caller's barrier); contains one __syncthreads().
-template <bool UNSCALE, int MBW, int NBW, int WM, int ROWS, class Acc, class Off>
+//
+// THE ACTIVATION TAIL (Tail = ActAmaxTail: the folded-inference products, whose BatchNorm sits in the weights).  Selected at compile
+// time: with Tail = NoTail (every training instantiation) none of it exists.  Behind the bias:
+//   v = v > 0 ? v : v * slope  (slope 0: ReLU);  store;
+//   amax emission (table != nullptr): the consumer of y is another f16x2 product and scales its operand by y's amax buffer
+//   (include/pvcnn_hip.h).  Of the STORED elements only (col_ok && row < row_limit) a lane keeps the largest |v| per column block (fmaxf: the
+//   inputs are finite; a NaN would not be recorded), the lanes of the workgroup meet in one LDS word per position segment of the tile (seg_local(nb): the lane's segment
+//   inside the tile, < nseg <= 256), and one vector atomicMax per (workgroup, segment) combines the row tiles in table[1 + seg_index(l)]
+//   (seg_index(l) < 0: a segment of the tile outside the tensor).  Non-negative floats order like their bit patterns, so the result
+//   does not depend on the order; the caller has zeroed the table.  Word [0] is never written (a table-only buffer).
+//   The tail brings three barriers of its own and needs no barrier from the caller; every thread of the workgroup must arrive.
+struct NoTail {};
+template <class SegLocal, class SegIndex>
+struct ActAmaxTail {
+  float slope;
+  uint32_t *table;
+  int nseg;
+  SegLocal seg_local;          // (column block nb) -> the lane's segment inside the tile; asked after the stores, not kept across them
+  SegIndex seg_index;
+};
+template <class SegLocal, class SegIndex>
+__device__ __forceinline__ ActAmaxTail<SegLocal, SegIndex> act_amax_tail(float slope, uint32_t *table, int nseg, SegLocal seg_local, SegIndex seg_index) {
+  return ActAmaxTail<SegLocal, SegIndex>{slope, table, nseg, seg_local, seg_index};
+}
+// kernel arguments of the tail: nothing for the instantiations without it
+template <bool ACT> struct ActArgs {};
+template <> struct ActArgs<true> { float slope; uint32_t *amax; };
+__device__ __forceinline__ float act_tail(float v, float slope) { return v > 0.0f ? v : v * slope; }
+__device__ __forceinline__ uint32_t act_abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+  return m;
+}
+// segment l of a Conv3d tile = its z row (xt, yt) = (l / TY, l % TY)  ->  row (b, x0 + xt, y0 + yt) of the (B, R, R) table
+template <int TY>
+struct ZRowIndex {
+  int b, R, x0, y0;
+  __device__ __forceinline__ long operator()(int l) const {
+    const int gx = x0 + l / TY, gy = y0 + l % TY;
+    return (gx < R && gy < R) ? ((long)b * R + gx) * R + gy : -1L;
+  }
+};
+// a 1x1 tile is one 256-point segment: the tile's index
+struct TileIndex {
+  long tile;
+  __device__ __forceinline__ long operator()(int) const { return tile; }
+};
+
+template <bool UNSCALE, int MBW, int NBW, int WM, int ROWS, class Acc, class Off, class Tail = NoTail>
 __device__ __forceinline__ void gemm_tile_epilogue(Acc acc, float *__restrict__ yb, size_t row_stride, const Off (&col_off)[NBW],
                                                    const bool (&col_ok)[NBW], int row0, int row_limit, const float *__restrict__ bias,
                                                    const int *__restrict__ wexp, int x_shift, float2 *__restrict__ stats_part,
-                                                   size_t stats_stride, size_t stats_slot, float2 *stat_lds) {
+                                                   size_t stats_stride, size_t stats_slot, float2 *stat_lds, const Tail &tail = Tail{}) {
+  constexpr bool ACT = !std::is_same<Tail, NoTail>::value;
+  [[maybe_unused]] float am[NBW];                              // max |v| of the lane's stored elements per column block
+  if constexpr (ACT) {
+#pragma unroll
+    for (int nb = 0; nb < NBW; ++nb) am[nb] = 0.0f;
+  }
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, kh = lane >> 5;
   const int wm = wave % WM, wn = wave / WM;
   const bool want_stats = stats_part != nullptr;
@@ -60,6 +116,10 @@ __device__ __forceinline__ void gemm_tile_epilogue(Acc acc, float *__restrict__ 
           qq[r] += m * m;
         }
         v += bv[r];
+        if constexpr (ACT) {
+          v = act_tail(v, tail.slope);
+          if (col_ok[nb] && row < row_limit) am[nb] = fmaxf(am[nb], fabsf(v));
+        }
         if (col_ok[nb] && row < row_limit) col[(size_t)row * row_stride] = v;
       }
     }
@@ -76,6 +136,28 @@ __device__ __forceinline__ void gemm_tile_epilogue(Acc acc, float *__restrict__ 
 #pragma unroll
       for (int w = 1; w < 4 / WM; ++w) { t.x += stat_lds[w * ROWS + tid].x; t.y += stat_lds[w * ROWS + tid].y; }
       stats_part[(size_t)(row0 + tid) * stats_stride + stats_slot] = t;
+    }
+  }
+  if constexpr (ACT) {
+    if (tail.table != nullptr) {                                // (uniform: a kernel argument)
+      uint32_t *amax_lds = reinterpret_cast<uint32_t *>(stat_lds);
+      __syncthreads();                                          // the tile / the statistics in this LDS have been read
+      if (tid < tail.nseg) amax_lds[tid] = 0u;
+      __syncthreads();
+#pragma unroll
+      for (int nb = 0; nb < NBW; ++nb) {
+        const uint32_t mine = __float_as_uint(am[nb]);
+        const uint32_t m = max(mine, (uint32_t)__shfl_xor((int)mine, 32));         // the two row halves of the lane's column
+        if (kh == 0 && m != 0u) atomicMax(&amax_lds[tail.seg_local(nb)], m);       // (m != 0: the column was stored)
+      }
+      __syncthreads();
+      if (tid < tail.nseg) {
+        const uint32_t m = amax_lds[tid];
+        int l = tid;
+        asm volatile("" : "+v"(l));                             // (derived here: hoisted to the kernel's start, l / TY costs the 256-register tiles a spill)
+        const long t = tail.seg_index(l);
+        if (m != 0u && t >= 0) atomicMax(tail.table + 1 + t, m);
+      }
     }
   }
 }

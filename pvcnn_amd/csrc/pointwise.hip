@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "gemm_epilogue.h"
 
 namespace pvcnn {
 
@@ -50,10 +51,13 @@ __global__ __launch_bounds__(256) void pw_transpose_kernel(const float *__restri
 //   chunks are software-pipelined -- chunk k+1's global loads are issued before chunk k's MFMA loop and
 //   land in LDS after it.  Otherwise: bounds-checked scalar staging, same MFMA loop.
 // ---------------------------------------------------------------------------------------------
-template <int MB, bool FAST, bool BIAS>
+//   ACT: the activation tail (the contract stated at gemm_tile_epilogue, in this kernel's own text): LeakyReLU(aa.slope) behind the
+//   bias; the workgroup's 256 points are one segment of y's amax table, each wave reduces in registers and issues one atomicMax.
+template <int MB, bool FAST, bool BIAS, bool ACT = false>
 __global__ __launch_bounds__(256) void pw_gemm_kernel(const float *__restrict__ x, const float *__restrict__ wt,
                                                       const float *__restrict__ bias, float *__restrict__ y, int K, int M,
-                                                      int N, int tiles_n, int tiles_total, float2 *__restrict__ stats_part) {
+                                                      int N, int tiles_n, int tiles_total, float2 *__restrict__ stats_part,
+                                                      ActArgs<ACT> aa) {
   constexpr int TM = 32 * MB;
   __shared__ __attribute__((aligned(16))) float xs[kPwK * kPwN];
   __shared__ __attribute__((aligned(16))) float ws[kPwK * TM];
@@ -170,6 +174,7 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(const float *__restrict__ 
   float2 *stat_lds = reinterpret_cast<float2 *>(xs);        // [4 waves][TM]
   if (want_stats) __syncthreads();                          // all waves are done reading xs / ws
   float *yb = y + (size_t)b * M * N;
+  [[maybe_unused]] uint32_t am = 0u;
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) {
     if (FAST && m0 + mb * 32 >= M) break;                  // FAST: M % 32 == 0, whole row blocks in or out
@@ -198,6 +203,10 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(const float *__restrict__ 
           qq[r] += mv * mv;
         }
         v += bv[r];
+        if constexpr (ACT) {
+          v = act_tail(v, aa.slope);
+          if (FAST || (n < N && m < M)) am = max(am, act_abs_bits(v));
+        }
         if (FAST || (n < N && m < M)) yb[(size_t)m * N + n] = v;
       }
     }
@@ -215,6 +224,12 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(const float *__restrict__ 
 #pragma unroll
       for (int w = 1; w < 4; ++w) { t.x += stat_lds[w * TM + tid].x; t.y += stat_lds[w * TM + tid].y; }
       stats_part[(size_t)(m0 + tid) * tiles_total + tile] = t;
+    }
+  }
+  if constexpr (ACT) {
+    if (aa.amax != nullptr) {
+      am = wave_max_u32(am);
+      if (lane == 0 && am != 0u) atomicMax(aa.amax + 1 + tile, am);
     }
   }
 }
@@ -531,8 +546,9 @@ extern "C" int pvcnn_pwconv_transpose(const float *w, int M, int K, float *wt, v
   return check_launch("pwconv_transpose");
 }
 
+template <bool ACT = false>
 static int pwconv_fwd_impl(const float *x, const float *wt, int wt_rows, const float *bias, int B, int K, int M, int N, float *y,
-                           float2 *stats_part, hipStream_t s) {
+                           float2 *stats_part, hipStream_t s, ActArgs<ACT> aa = {}) {
   const int tiles_n = ceil_div(N, kPwN);
   const int MB = M > 64 ? 4 : 2;                         // output channels per workgroup: 128 or 64
   const long tiles_total = (long)B * tiles_n;
@@ -543,8 +559,8 @@ static int pwconv_fwd_impl(const float *x, const float *wt, int wt_rows, const f
   const bool fast = (wt_rows >= ceil_div(K, kPwK) * kPwK) && (N % kPwN == 0) && (M % 32 == 0) && aligned16(x) && aligned16(wt);
 #define PVCNN_PW_LAUNCH(MBV, FASTV)                                                                                   \
   do {                                                                                                                \
-    if (bias) hipLaunchKernelGGL((pw_gemm_kernel<MBV, FASTV, true>), grid, dim3(256), 0, s, x, wt, bias, y, K, M, N, tiles_n, (int)tiles_total, stats_part);  \
-    else      hipLaunchKernelGGL((pw_gemm_kernel<MBV, FASTV, false>), grid, dim3(256), 0, s, x, wt, bias, y, K, M, N, tiles_n, (int)tiles_total, stats_part); \
+    if (bias) hipLaunchKernelGGL((pw_gemm_kernel<MBV, FASTV, true, ACT>), grid, dim3(256), 0, s, x, wt, bias, y, K, M, N, tiles_n, (int)tiles_total, stats_part, aa);  \
+    else      hipLaunchKernelGGL((pw_gemm_kernel<MBV, FASTV, false, ACT>), grid, dim3(256), 0, s, x, wt, bias, y, K, M, N, tiles_n, (int)tiles_total, stats_part, aa); \
   } while (0)
   if (MB == 4) { if (fast) PVCNN_PW_LAUNCH(4, true); else PVCNN_PW_LAUNCH(4, false); }
   else         { if (fast) PVCNN_PW_LAUNCH(2, true); else PVCNN_PW_LAUNCH(2, false); }
@@ -560,6 +576,19 @@ extern "C" int pvcnn_pwconv_fwd(const float *x, const float *wt, int wt_rows, co
   PVCNN_REQUIRE((long)N * std::max(K, M) <= 0x7fffffffL, "cloud too large");
   PVCNN_REQUIRE(wt_rows >= K, "wt has fewer rows than K");
   return pwconv_fwd_impl(x, wt, wt_rows, bias, B, K, M, N, y, nullptr, static_cast<hipStream_t>(stream));
+}
+
+// pvcnn_pwconv_fwd with the activation tail (include/pvcnn_hip.h): y = LeakyReLU(wt^T x + bias, slope), y's amax table emitted
+extern "C" int pvcnn_pwconv_fwd_act(const float *x, const float *wt, int wt_rows, const float *bias, int B, int K, int M, int N,
+                                    float *y, float slope, void *y_amax, int y_amax_seg, void *stream) {
+  PVCNN_REQUIRE(B >= 0 && K > 0 && M > 0 && N >= 0, "bad size");
+  PVCNN_REQUIRE(!y_amax || y_amax_seg == kPwN, "y_amax_seg must be 256 (one maximum per point tile)");
+  if (B == 0 || N == 0) return 0;
+  PVCNN_REQUIRE(x && wt && y, "null pointer");
+  PVCNN_REQUIRE((long)N * std::max(K, M) <= 0x7fffffffL, "cloud too large");
+  PVCNN_REQUIRE(wt_rows >= K, "wt has fewer rows than K");
+  return pwconv_fwd_impl<true>(x, wt, wt_rows, bias, B, K, M, N, y, nullptr, static_cast<hipStream_t>(stream),
+                               ActArgs<true>{slope, static_cast<uint32_t *>(y_amax)});
 }
 
 extern "C" size_t pvcnn_pwconv_fwd_stats_parts(int B, int N) {

@@ -129,10 +129,11 @@ __global__ __launch_bounds__(256) void pw_weight_split_f16_batch_kernel(const Sp
 
 // ---- epilogue of the 1x1 GEMM kernels: D[i = m][j = point]; lanes = consecutive points (128-byte rows of (B, M, N)); the rest is
 // gemm_tile_epilogue.  `lds` = the workgroup's staging buffer (>= 4 / WM * TM float pairs), free after the barrier.
-template <int NS, int MB, int WM>
+// ACT: the activation tail (gemm_epilogue.h) -- the workgroup's 256-point tile is one segment of y's amax table, entry `tile`.
+template <int NS, int MB, int WM, bool ACT = false>
 __device__ __forceinline__ void pb_epilogue(f32x16 (&acc)[MB / WM][2 * WM], uint32_t *lds, const float *__restrict__ bias,
                                             float *__restrict__ y, int M, int N, int b, int n0, int m0, int tile, int tiles_total,
-                                            float2 *__restrict__ stats_part, const int *__restrict__ wexp, int x_shift) {
+                                            float2 *__restrict__ stats_part, const int *__restrict__ wexp, int x_shift, ActArgs<ACT> aa = {}) {
   constexpr int NBW = 2 * WM;
   const int wn = (threadIdx.x >> 6) / WM, j = threadIdx.x & 31;
   int n[NBW];
@@ -143,8 +144,14 @@ __device__ __forceinline__ void pb_epilogue(f32x16 (&acc)[MB / WM][2 * WM], uint
     nok[nb] = n[nb] < N;
   }
   if (stats_part != nullptr) __syncthreads();
-  gemm_tile_epilogue<NS == 2, MB / WM, NBW, WM, 32 * MB>([&](int mbl, int nb, int r) { return acc[mbl][nb][r]; }, y + (size_t)b * M * N, N, n, nok, m0, M,
-                                                         bias, wexp, x_shift, stats_part, tiles_total, tile, reinterpret_cast<float2 *>(lds));
+  if constexpr (ACT) {
+    const auto tail = act_amax_tail(aa.slope, aa.amax, 1, [](int) { return 0; }, TileIndex{(long)tile});
+    gemm_tile_epilogue<NS == 2, MB / WM, NBW, WM, 32 * MB>([&](int mbl, int nb, int r) { return acc[mbl][nb][r]; }, y + (size_t)b * M * N, N, n, nok, m0, M,
+                                                           bias, wexp, x_shift, stats_part, tiles_total, tile, reinterpret_cast<float2 *>(lds), tail);
+  } else {
+    gemm_tile_epilogue<NS == 2, MB / WM, NBW, WM, 32 * MB>([&](int mbl, int nb, int r) { return acc[mbl][nb][r]; }, y + (size_t)b * M * N, N, n, nok, m0, M,
+                                                           bias, wexp, x_shift, stats_part, tiles_total, tile, reinterpret_cast<float2 *>(lds));
+  }
 }
 
 // f16x2 operand scale: amax_seg = 0 -> one scale for the whole tensor (x_absmax[0]); amax_seg = 256 -> x_absmax is an "amax buffer"
@@ -156,12 +163,12 @@ __device__ __forceinline__ void pb_epilogue(f32x16 (&acc)[MB / WM][2 * WM], uint
 // quad: those columns are never stored), the next weight fragments from a clamped chunk.  With branches around the loads the
 // compiler cannot count the loads in flight and waits with vmcnt(0) in front of the first MFMA of every chunk -- i.e. for the
 // prefetch it has just issued (ISA of round 3: the whole HBM latency was exposed once per chunk).
-template <int NS, int MB, int PF = 1, bool VEC = false>
+template <int NS, int MB, int PF = 1, bool VEC = false, bool ACT = false>
 __global__ __launch_bounds__(256, 2) void pw_gemm_bf16_kernel(const float *__restrict__ x, const uint16_t *__restrict__ wts,
                                                               const float *__restrict__ bias, float *__restrict__ y, int K, int M,
                                                               int N, int tiles_n, int tiles_total, float2 *__restrict__ stats_part,
                                                               const uint32_t *__restrict__ x_absmax, const int *__restrict__ wexp,
-                                                              int amax_seg) {
+                                                              int amax_seg, ActArgs<ACT> aa) {
   // Wave arrangement inside the 32*MB x 256 workgroup tile.  Each lane fetches its own A (weight) fragments from global memory:
   // with the four waves side by side along the points (WM = 1) every wave pulls ALL 32*MB rows through the CU's vector-memory
   // path -- at MB = 4 that is 48 KiB per chunk and workgroup (A four times + the x rows) = as many L1 cycles (64 B/clk) as the
@@ -306,7 +313,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16_kernel(const float *__res
   }
   }
 
-  pb_epilogue<NS, MB, WM>(acc, xs, bias, y, M, N, b, n0, m0, tile, tiles_total, stats_part, wexp, x_shift);
+  pb_epilogue<NS, MB, WM, ACT>(acc, xs, bias, y, M, N, b, n0, m0, tile, tiles_total, stats_part, wexp, x_shift, aa);
 }
 
 // The wide f16x2 tile (NS = 2, MB = 4, vector loads) with the conversion INSIDE the multiply phase: the staging buffer is double-
@@ -317,12 +324,12 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16_kernel(const float *__res
 // load has a whole chunk to land: the weight fragments of chunk c + 1 are requested in front of chunk c's MFMAs (second register set),
 // and the loop is straight-line code, so the compiler's vmcnt waits leave the younger loads in flight.  (pw_gemm_bf16_kernel converts between two barriers and relies on the co-resident workgroup to fill the
 // matrix pipe meanwhile.)  Same products in the same order per output element: bit-identical to pw_gemm_bf16_kernel<2, 4>.
-template <int NS>   // 2 = f16x2; 1 = plain bf16 operands (torch.autocast): one plane, one product -- the conversion is then the longer phase
+template <int NS, bool ACT = false>   // 2 = f16x2; 1 = plain bf16 operands (torch.autocast): one plane, one product -- the conversion is then the longer phase
 __global__ __launch_bounds__(256, 2) void pw_gemm_f16_pipe_kernel(const float *__restrict__ x, const uint16_t *__restrict__ wts,
                                                                   const float *__restrict__ bias, float *__restrict__ y, int K, int M,
                                                                   int N, int tiles_n, int tiles_total, float2 *__restrict__ stats_part,
                                                                   const uint32_t *__restrict__ x_absmax, const int *__restrict__ wexp,
-                                                                  int amax_seg) {
+                                                                  int amax_seg, ActArgs<ACT> aa) {
   static_assert(NS == 1 || NS == 2, "f16x2 or bf16");
   constexpr int MB = 4, TM = 32 * MB, WM = 2, MBW = MB / WM, NBW = 2 * WM, WBLK = NS * TM * kPbK;
   constexpr int ITEMS = (kPbK / 2) * (kPbN / 4) / 256, TILE = NS * 8 * kPbN;
@@ -442,7 +449,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f16_pipe_kernel(const float *_
       __syncthreads();
     }
   }
-  pb_epilogue<NS, MB, WM>(acc, xs, bias, y, M, N, b, n0, m0, tile, tiles_total, stats_part, wexp, x_shift);
+  pb_epilogue<NS, MB, WM, ACT>(acc, xs, bias, y, M, N, b, n0, m0, tile, tiles_total, stats_part, wexp, x_shift, aa);
 }
 
 // ---- the 256 x 256 f16x2 tile, ONE workgroup per CU, persistent (round 6) ---------------------------------------------------------
@@ -490,6 +497,8 @@ template <int WMW> struct WideGeom {
 // AB (ablation bits, tools/probe builds only; the library instantiates 0): 1 = no A requests in the step loop, 2 = no row requests,
 // 4 = no conversion / tile store, 8 = no B reads, 16 = no step barrier -- the step then multiplies stale fragments: wrong results, the
 // MFMAs and everything else stay, and the difference in time is what the removed part costs (phase clocks perturb too much here).
+// (No activation tail here: with it the kernel needs 12 .. 23 registers more than the 512 it has and spills.  The *_act entry point
+// sends these shapes to the bit-identical 128-row kernels: pwconv_fwd_split_impl.)
 template <int WMW, int AB = 0>
 __global__ __launch_bounds__(256, 1) void pw_gemm_f16_wide_kernel(const float *__restrict__ x, const uint16_t *__restrict__ wts,
                                                                   const float *__restrict__ bias, float *__restrict__ y, int K, int M,
@@ -902,8 +911,9 @@ extern "C" int pvcnn_pwconv_fwd_split_route(int B, int K, int M, int N, int nspl
 
 // y (B,M,N) = W x + bias with the pre-split weights (forward: K = Ci, M = Co; backward-data: x = grad_y, K = Co, M = Ci, bias NULL,
 // for_bwd_data = 1 image).  stats_part: NULL or (M, *_split_stats_parts) float pairs of (sum, sum of squares) of (y - bias).
-extern "C" int pvcnn_pwconv_fwd_split(const float *x, const void *wts, const float *bias, int B, int K, int M, int N, int nsplit,
-                                      const void *x_absmax, int amax_seg, float *y, float *stats_part, void *stream) {
+template <bool ACT>
+static int pwconv_fwd_split_impl(const float *x, const void *wts, const float *bias, int B, int K, int M, int N, int nsplit,
+                                 const void *x_absmax, int amax_seg, float *y, float *stats_part, void *stream, ActArgs<ACT> aa) {
   PVCNN_REQUIRE(B >= 0 && K > 0 && M > 0 && N >= 0, "bad size");
   PVCNN_REQUIRE(amax_seg == 0 || amax_seg == kPbN, "amax_seg must be 0 (scalar scale) or 256 (one maximum per point tile)");
   PVCNN_REQUIRE(nsplit >= 1 && nsplit <= 3, "nsplit must be 1 (bf16), 2 (f16x2) or 3 (bf16x3)");
@@ -912,7 +922,9 @@ extern "C" int pvcnn_pwconv_fwd_split(const float *x, const void *wts, const flo
   PVCNN_REQUIRE(x && wts && y && aligned16(wts), "null or misaligned pointer");
   PVCNN_REQUIRE(!stats_part || (reinterpret_cast<uintptr_t>(stats_part) & 7) == 0, "stats_part must be 8-byte aligned");
   PVCNN_REQUIRE((long)N * std::max(K, M) <= 0x7fffffffL, "cloud too large");
-  const route::PwFwdPlan p = route::pwconv_fwd_split_plan(B, K, M, N, nsplit, aligned16(x), switches());
+  Switches sw = switches();
+  if (ACT) sw.pw_wide = 0;          // the persistent kernel has no registers for the tail: its shapes take the bit-identical 128-row kernels
+  const route::PwFwdPlan p = route::pwconv_fwd_split_plan(B, K, M, N, nsplit, aligned16(x), sw);
   PVCNN_REQUIRE(p.grid <= 0x7fffffffL, "grid too large");
   const dim3 grid((unsigned)p.grid);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -924,11 +936,11 @@ extern "C" int pvcnn_pwconv_fwd_split(const float *x, const void *wts, const flo
   hipLaunchKernelGGL((KERNEL), grid, dim3(256), LDS, s, x, w16, bias, y, K, M, N, p.tiles_n, (int)p.tiles_total, sp, am, wexp, amax_seg, ##__VA_ARGS__)
 #define PVCNN_PB_GEMM(NSV, MBV, PFV)                                                                \
   do {                                                                                              \
-    if (p.vec) PVCNN_PB_LAUNCH((pw_gemm_bf16_kernel<NSV, MBV, PFV, true>), 0);                         \
-    else PVCNN_PB_LAUNCH((pw_gemm_bf16_kernel<NSV, MBV, PFV, false>), 0);                              \
+    if (p.vec) PVCNN_PB_LAUNCH((pw_gemm_bf16_kernel<NSV, MBV, PFV, true, ACT>), 0, aa);                         \
+    else PVCNN_PB_LAUNCH((pw_gemm_bf16_kernel<NSV, MBV, PFV, false, ACT>), 0, aa);                              \
   } while (0)
   switch (p.kernel) {
-    case route::PwKernel::Wide: {
+    case route::PwKernel::Wide: if constexpr (!ACT) {
       const unsigned xb = (unsigned)((size_t)B * K * N * 4), wb = (unsigned)pb_image_bytes(K, M, 2);
 #define PVCNN_WIDE_LAUNCH(ABV)                                                                      \
       do {                                                                                          \
@@ -950,10 +962,10 @@ extern "C" int pvcnn_pwconv_fwd_split(const float *x, const void *wts, const flo
       PVCNN_WIDE_LAUNCH(0);
 #endif
 #undef PVCNN_WIDE_LAUNCH
-      break;
     }
+      break;
     case route::PwKernel::Pipe:
-      if (nsplit == 2) PVCNN_PB_LAUNCH((pw_gemm_f16_pipe_kernel<2>), 0); else PVCNN_PB_LAUNCH((pw_gemm_f16_pipe_kernel<1>), 0);
+      if (nsplit == 2) PVCNN_PB_LAUNCH((pw_gemm_f16_pipe_kernel<2, ACT>), 0, aa); else PVCNN_PB_LAUNCH((pw_gemm_f16_pipe_kernel<1, ACT>), 0, aa);
       break;
     case route::PwKernel::Gemm:
       if (nsplit == 3)      { if (p.mb == 4) PVCNN_PB_GEMM(3, 4, 1); else PVCNN_PB_GEMM(3, 2, 1); }
@@ -964,4 +976,19 @@ extern "C" int pvcnn_pwconv_fwd_split(const float *x, const void *wts, const flo
 #undef PVCNN_PB_GEMM
 #undef PVCNN_PB_LAUNCH
   return check_launch("pwconv_fwd_split");
+}
+
+extern "C" int pvcnn_pwconv_fwd_split(const float *x, const void *wts, const float *bias, int B, int K, int M, int N, int nsplit,
+                                      const void *x_absmax, int amax_seg, float *y, float *stats_part, void *stream) {
+  return pwconv_fwd_split_impl<false>(x, wts, bias, B, K, M, N, nsplit, x_absmax, amax_seg, y, stats_part, stream, ActArgs<false>{});
+}
+
+// pvcnn_pwconv_fwd_split with the activation tail (include/pvcnn_hip.h): y = LeakyReLU(W x + bias, slope); y_amax: NULL or y's zeroed
+// amax buffer, whose table the epilogues fill (y_amax_seg = 256)
+extern "C" int pvcnn_pwconv_fwd_split_act(const float *x, const void *wts, const float *bias, int B, int K, int M, int N, int nsplit,
+                                          const void *x_absmax, int amax_seg, float *y, float *stats_part, float slope, void *y_amax,
+                                          int y_amax_seg, void *stream) {
+  PVCNN_REQUIRE(!y_amax || y_amax_seg == kPbN, "y_amax_seg must be 256 (one maximum per point tile)");
+  return pwconv_fwd_split_impl<true>(x, wts, bias, B, K, M, N, nsplit, x_absmax, amax_seg, y, stats_part, stream,
+                                     ActArgs<true>{slope, static_cast<uint32_t *>(y_amax)});
 }

@@ -805,6 +805,61 @@ class HipBackend:
         _f32(grad_y, 'grad_y'); _f32(weight, 'weight')
         return self._product_split(PW, grad_y, self._weight_split(PW, weight, True, nsplit), None, weight.shape[1], nsplit, False, amax)
 
+    # ---- the activation tail (include/pvcnn_hip.h: the *_act entry points): y = LeakyReLU(product + bias, act_slope) written once,
+    # and y's amax buffer emitted by the same epilogues -- what an eval-mode [conv, BatchNorm, activation] triple is once the
+    # BatchNorm sits in the weights (functional/_fold.py).  Counterparts of conv3d_igemm_split / pwconv_gemm_split / conv3d_forward /
+    # pwconv_forward on PREPARED weights (nothing is split or transposed here); each -> (y, y's amax buffer | None).
+    has_product_act = True
+
+    def _amax_table(self, p, b, l, device, emit):
+        """-> (y's zeroed table-only amax buffer -- the epilogues combine into it with atomicMax --, its segment length) or (None, 0)."""
+        if not emit:
+            return None, 0
+        seg = p.amax_seg(self, l)
+        return torch.zeros((1 + p.amax_tiles(b, l, seg),), dtype=torch.int32, device=device), seg
+
+    def _product_split_act(self, p, x, wts, bias, co, nsplit, act_slope, amax=None, emit_amax=True):
+        b, ci, l = x.shape[0], x.shape[1], x.shape[2]
+        y = torch.empty(p.out_shape(b, co, l), dtype=torch.float32, device=x.device)
+        seg = 0
+        if int(nsplit) == 2:
+            amax, seg = self._amax_for(p, x, amax)
+        table, yseg = self._amax_table(p, b, l, x.device, emit_amax)
+        _run(p.entry(self.lib, 'fwd_split_act'), f'{p.c}_forward_split_act', x, x, wts, bias, b, ci, co, l, int(nsplit), amax, seg, y, None,
+             float(act_slope), table, yseg)
+        return y, table
+
+    def conv3d_igemm_split_act(self, x, wts, bias, co, nsplit, act_slope, amax=None, emit_amax=True):
+        """conv3d_igemm_split + the activation tail: -> (y (B,co,R,R,R), y's amax buffer with one maximum per z row | None)."""
+        return self._product_split_act(CONV, x, wts, bias, co, nsplit, act_slope, amax, emit_amax)
+
+    def pwconv_gemm_split_act(self, x, wts, bias, m, nsplit, act_slope, amax=None, emit_amax=True):
+        """pwconv_gemm_split + the activation tail: -> (y (B,m,N), y's amax buffer with one maximum per 256 points | None)."""
+        return self._product_split_act(PW, x, wts, bias, m, nsplit, act_slope, amax, emit_amax)
+
+    def conv3d_forward_act(self, x, wt, bias, co, act_slope, emit_amax=True):
+        """The fp32-MFMA Conv3d on a transformed weight (`_conv_wt`) + the activation tail."""
+        b, ci, r = x.shape[0], x.shape[1], x.shape[2]
+        y = torch.empty((b, co, r, r, r), dtype=torch.float32, device=x.device)
+        table, yseg = self._amax_table(CONV, b, r, x.device, emit_amax)
+        _run(self.lib.pvcnn_conv3d_fwd_act, 'conv3d_forward_act', x, x, wt, bias, b, ci, co, r, y, float(act_slope), table, yseg)
+        return y, table
+
+    def pwconv_weight_transposed(self, weight):
+        """(Co,Ci) -> the (K32,Co) layout pvcnn_pwconv_fwd takes (K rounded up to the 32-channel chunk, zero tail)."""
+        co, ci = weight.shape
+        wt = torch.empty(((ci + 31) // 32 * 32, co), dtype=torch.float32, device=weight.device)
+        _run(self.lib.pvcnn_pwconv_transpose, 'pwconv_transpose', weight, weight, co, ci, wt)
+        return wt
+
+    def pwconv_forward_act(self, x, wt, bias, co, act_slope, emit_amax=True):
+        """The fp32-MFMA 1x1 GEMM on a transposed weight (`pwconv_weight_transposed`) + the activation tail."""
+        b, ci, n = x.shape
+        y = torch.empty((b, co, n), dtype=torch.float32, device=x.device)
+        table, yseg = self._amax_table(PW, b, n, x.device, emit_amax)
+        _run(self.lib.pvcnn_pwconv_fwd_act, 'pwconv_forward_act', x, x, wt, wt.shape[0], bias, b, ci, co, n, y, float(act_slope), table, yseg)
+        return y, table
+
     def pwconv_backward_weight(self, x, grad_y, with_bias=False, out_w=None, out_b=None):
         """-> grad_weight (Co,Ci), or (grad_weight, grad_bias) when with_bias."""
         _f32(x, 'x'); _f32(grad_y, 'grad_y')

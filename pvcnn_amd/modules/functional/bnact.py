@@ -13,8 +13,10 @@ import torch
 import torch.nn as nn
 from torch.autograd import Function
 
-from . import _cache, _gradslots
+from . import _cache, _fold, _gradslots, _product
+from ._align import aligned as _aligned
 from ._autograd import native, amp_fwd, amp_bwd
+from ._fold import folded_parameters
 from .backend import batch_strided_ok
 from .devoxelization import CornerTaps
 
@@ -89,7 +91,8 @@ def _statistics(x3, use_batch_stats, stats_part, stats_shift, running_mean, runn
     return running_mean.contiguous(), torch.rsqrt(running_var + eps)
 
 
-__all__ = ['batch_norm_act', 'batch_norm_act_devoxelize', 'batch_norm_act_se_devoxelize', 'fusable_tail', 'run_layers', 'fused_dropout_ok']
+__all__ = ['batch_norm_act', 'batch_norm_act_devoxelize', 'batch_norm_act_se_devoxelize', 'fusable_tail', 'run_layers', 'fused_dropout_ok',
+           'folded_parameters', 'folded_snapshot']
 
 
 class BatchNormAct(Function):
@@ -417,6 +420,56 @@ def _wants_batch_stats(m):
     return isinstance(m, nn.modules.batchnorm._BatchNorm) and (m.training or m.running_mean is None)
 
 
+def folded_snapshot(conv, bn, act):
+    """The snapshot `run_layers` runs in place of the three modules [conv, bn, act], or None: a valid one sits on the convolution
+    (pvcnn_amd.fold_batchnorm; functional/_fold.py: never stale), `bn` is a BatchNorm in eval mode with running statistics, `act` a
+    ReLU / LeakyReLU, and gradients are disabled.  Cheap where nothing was folded: one attribute lookup."""
+    if getattr(conv, _fold.ATTR, None) is None:
+        return None
+    if not isinstance(bn, nn.modules.batchnorm._BatchNorm) or _slope(act) is None:
+        return None
+    return _fold.snapshot_for(conv, bn)
+
+
+def _folded_kind(conv, x):
+    """-> (the product kind whose kernels serve `conv` on x, its arithmetic mode) or None: a SharedMLP 1x1 convolution or a PVConv
+    Conv3d on its fast path, fp32 features on the GPU."""
+    be = native()
+    if not (x.is_cuda and x.dtype == torch.float32 and x.numel() > 0 and getattr(be, 'has_product_act', False)):
+        return None
+    if _is_pointwise(conv) and getattr(be, 'has_pwconv', False) and x.dim() == len(conv.kernel_size) + 2:
+        from .pwconv import pw_nsplit
+        return _product.PW, pw_nsplit(x, conv.weight)
+    if hasattr(conv, 'forward_with_stats') and hasattr(conv, '_fast') and conv._fast(x):
+        from .conv3d import conv_nsplit
+        return _product.CONV, conv_nsplit()
+    return None
+
+
+def _folded_product(p, nsplit, snap, given, slope):
+    """act(bn(conv(given))) as ONE product on the snapshot's folded weights: the kernel's epilogue applies the activation and emits
+    the amax table of what it writes (tagged on the result like a BatchNorm pass's: the next product finds it there)."""
+    be = native()
+    x = p.canon(_aligned(given))
+    co = snap.weight.shape[0]
+    y_shape = (given.shape[0], co, *given.shape[2:])
+    emit = _amax_seg_for(y_shape, True) > 0
+    if nsplit == 0 and p is _product.PW:
+        y, table = be.pwconv_forward_act(x, snap.image(0, lambda w: be.pwconv_weight_transposed(p.canon_w(w))), snap.bias, co, slope, emit)
+    elif nsplit == 0:
+        y, table = be.conv3d_forward_act(x, snap.image(0, lambda w: be._conv_wt(w, False)), snap.bias, co, slope, emit)
+    else:
+        amax = None
+        if nsplit == 2:       # the input's scale table: left on the tensor by the pass that wrote it, else one read of it
+            amax = _cache.amax_of(given, p.amax_seg(be, x.shape[2]))
+            if amax is None:
+                amax = getattr(be, p.amax)(x, want_global=False)
+        image = snap.image(nsplit, lambda w: be._weight_split(p, p.canon_w(w), False, nsplit))
+        y, table = getattr(be, p.product_split + '_act')(x, image, snap.bias, co, nsplit, slope, amax=amax, emit_amax=emit)
+    y = p.shaped(y, y_shape)
+    return _cache.tag_amax(y, _amax_seg_for(y_shape, True), table) if table is not None else y
+
+
 def run_layers(layers, x, stop=None, tail_stats=False, tail_dropout=0.0):
     """nn.Sequential.forward with the GPU path's own kernels: 1x1 convolutions as channel-major MFMA GEMMs,
     (BatchNorm, ReLU|LeakyReLU) pairs fused, and the statistics of a BatchNorm that directly follows one of our
@@ -440,7 +493,13 @@ def run_layers(layers, x, stop=None, tail_stats=False, tail_dropout=0.0):
         nxt = all_mods[i + 1] if i + 1 < len(all_mods) else None
         want = fuse and _servable(x) and _wants_batch_stats(nxt)
         part = None
-        if pw and _is_pointwise(m) and _servable(x) and x.dim() == len(m.kernel_size) + 2 and x.numel() > 0:
+        # folded inference (pvcnn_amd.fold_batchnorm): [conv, BatchNorm, activation] as one product, decided per triple
+        snap = folded_snapshot(m, nxt, mods[i + 2]) if (i + 2 < len(mods) and not hooked and getattr(m, _fold.ATTR, None) is not None) else None
+        kind = _folded_kind(m, x) if snap is not None else None
+        if kind is not None and not (tail_dropout and i + 3 == len(mods)):
+            x = _folded_product(kind[0], kind[1], snap, x, _slope(mods[i + 2]))
+            i += 3
+        elif pw and _is_pointwise(m) and _servable(x) and x.dim() == len(m.kernel_size) + 2 and x.numel() > 0:
             from .pwconv import pointwise_conv, pw_nsplit
             split = pw_nsplit(x, m.weight)        # decided HERE: inside the autograd node autocast is already switched off
             if want:
