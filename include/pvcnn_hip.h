@@ -484,6 +484,15 @@ PVCNN_API int pvcnn_trilinear_devox_bnact_fwd(const float *coords, const float *
                                     const float *beta, const float *mean, const float *rstd, float slope,
                                     int B, int C, int N, int R, int is_training, int32_t *inds, float *wgts,
                                     const float *addend, const float *se_scale, float *outs, void *stream);
+/* As pvcnn_trilinear_devox_bnact_fwd (no se_scale), with `addend` (B,C,N, required) the PRE-BatchNorm point branch of the PVConv:
+ * outs = devoxelized + act(bn(addend)), the addend's BatchNorm (add_gamma / add_beta: C or NULL; add_mean / add_rstd: C) and
+ * ReLU | LeakyReLU(add_slope) applied to the addend quad where the store adds it.  Bit-identical to pvcnn_bnact_fwd on the addend
+ * followed by pvcnn_trilinear_devox_bnact_fwd; the activated point branch is never written. */
+PVCNN_API int pvcnn_trilinear_devox_bnact_addbn_fwd(const float *coords, const float *feat, const float *gamma,
+                                    const float *beta, const float *mean, const float *rstd, float slope,
+                                    int B, int C, int N, int R, int is_training, int32_t *inds, float *wgts,
+                                    const float *addend, const float *add_gamma, const float *add_beta,
+                                    const float *add_mean, const float *add_rstd, float add_slope, float *outs, void *stream);
 PVCNN_API int pvcnn_bnact_bwd(const float *x, const float *grad_y, const float *gamma, const float *beta,
                               const float *mean, const float *rstd, int B, int C, int S, float slope, int training,
                               float *grad_x, float *grad_gamma, float *grad_beta, void *workspace,

@@ -93,6 +93,7 @@ SIGNATURES = {
     'pvcnn_bn_finalize': (_i, [_vp, _i, ctypes.c_long, ctypes.c_double, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_long, _vp, _vp]),
     'pvcnn_bn_stats': (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     'pvcnn_trilinear_devox_bnact_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'pvcnn_trilinear_devox_bnact_addbn_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
     'pvcnn_bnact_slices': (_i, [_i]),
     'pvcnn_conv3d_weight_split_pair_entry': (_l, [_vp, _i, _i, _vp, _vp, _vp]),
     'pvcnn_conv3d_weight_split_pair_batch': (_i, [_vp, _i, _l, _vp]),

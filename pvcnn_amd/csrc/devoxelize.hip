@@ -67,6 +67,30 @@ extern "C" int pvcnn_trilinear_devox_bnact_fwd(const float *coords, const float 
   return launch_gather(p, feat, outs, B, C, /*L=*/R * R * R, /*J=*/N, vec, s, "trilinear_devox_bnact_fwd", xf, grid_pad_shift(R), addend);
 }
 
+// ... with the ADDEND pre-BatchNorm as well: the point branch's BatchNorm + ReLU | LeakyReLU (add_*: its parameters and statistics,
+// C each) is applied to the addend quad where the store adds it (slab.h, AddBnAct) -- the activated point branch is never written.
+extern "C" int pvcnn_trilinear_devox_bnact_addbn_fwd(const float *coords, const float *feat, const float *gamma,
+                                                     const float *beta, const float *mean, const float *rstd, float slope, int B,
+                                                     int C, int N, int R, int is_training, int32_t *inds, float *wgts,
+                                                     const float *addend, const float *add_gamma, const float *add_beta,
+                                                     const float *add_mean, const float *add_rstd, float add_slope, float *outs,
+                                                     void *stream) {
+  PVCNN_REQUIRE(B >= 0 && C > 0 && N >= 0 && R > 0, "bad size");
+  PVCNN_REQUIRE((long)R * R * R * sizeof(float) <= (size_t)kLdsBytesPerCU, "grid row does not fit LDS: use bnact_fwd + trilinear_devox_fwd");
+  if (B == 0 || N == 0) return 0;
+  PVCNN_REQUIRE(coords && outs && feat && mean && rstd, "null pointer");
+  PVCNN_REQUIRE(addend && add_mean && add_rstd, "the addend and its statistics are required: use pvcnn_trilinear_devox_bnact_fwd without");
+  PVCNN_REQUIRE(!is_training || (inds && wgts), "training mode needs inds and wgts");
+  PVCNN_REQUIRE(B <= 65535, "batch > 65535");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  TrilinearFromCoords p{coords, is_training ? inds : nullptr, is_training ? wgts : nullptr, N, R, R * R};
+  bool vec = (N % 4 == 0) && aligned16(coords) && aligned16(outs) && aligned16(addend);
+  if (is_training) vec = vec && aligned16(inds) && aligned16(wgts);
+  const XfBnAct xf{gamma, beta, mean, rstd, slope, nullptr};
+  const AddBnAct ax{add_gamma, add_beta, add_mean, add_rstd, add_slope};
+  return launch_gather(p, feat, outs, B, C, /*L=*/R * R * R, /*J=*/N, vec, s, "trilinear_devox_bnact_addbn_fwd", xf, grid_pad_shift(R), addend, ax);
+}
+
 extern "C" size_t pvcnn_trilinear_devox_bwd_workspace_bytes(int B, int C, int N, int R) {
   if (B <= 0 || C < 0 || N < 0 || R <= 0) return 0;
   const long S = (long)R * R * R;

@@ -305,6 +305,28 @@ struct XfBnAct {
   }
 };
 
+// Optional transform of the gather's ADDEND, applied where the store adds it ("gather + f(addend row)" without ever writing
+// f(addend) to memory).  AddPlain: the addend as it is.  AddBnAct: the addend is the PRE-BatchNorm point branch of a PVConv
+// (modules/pvconv.py:31-34,38); BatchNorm + LeakyReLU with the very expressions of bnact_apply_pb_kernel's forward (bnact.hip:
+// fmaf, then v > 0 ? v : v * slope -- slope 0 on a negative v yields -0 there and here), so the sum is bit-identical to adding
+// the tensor that pass would have written.  A row's (scale, shift) are uniform: scalar loads and scalar registers.
+struct AddPlain {
+  static constexpr bool kPlain = true;
+};
+struct AddBnAct {
+  static constexpr bool kPlain = false;
+  const float *gamma, *beta, *mean, *rstd;   // per channel; gamma / beta may be null
+  float slope;
+  __device__ __forceinline__ void params(int c, float &scale, float &shift) const {
+    scale = (gamma ? gamma[c] : 1.0f) * rstd[c];
+    shift = (beta ? beta[c] : 0.0f) - mean[c] * scale;
+  }
+  __device__ __forceinline__ float apply(float a, float scale, float shift) const {
+    const float v = fmaf(a, scale, shift);
+    return v > 0.f ? v : v * slope;
+  }
+};
+
 // one row of a slab through a transform (row = channel c of the cloud)
 template <int THREADS, class XF>
 __device__ __forceinline__ void slab_copy_row_xf(float *dst, const float *src, int len, const XF &xf, int c) {
@@ -377,11 +399,11 @@ __device__ __forceinline__ void slab_stage(float *lds, const float *src, int g, 
 // thread owns all of its elements in one pass (J <= THREADS*VEC, the usual case) their taps are fetched and
 // packed ONCE and stay in registers for all slabs: coordinates / indices are read from memory once per
 // SEQ*G channels instead of once per slab, and only "stream slab, barrier, LDS gather, store" repeats.
-template <class P, int VEC, int THREADS, bool RESIDENT, class XF, bool PAD>
+template <class P, int VEC, int THREADS, bool RESIDENT, class XF, bool PAD, class AX = AddPlain>
 __global__ __launch_bounds__(THREADS) void gather_lds_kernel(P p, XF xf, const float *__restrict__ src,
                                                              float *__restrict__ dst, int C, int L,
                                                              int J, int G, int SEQ, int pshift,
-                                                             const float *__restrict__ addend = nullptr) {
+                                                             const float *__restrict__ addend = nullptr, AX ax = AX{}) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int NC = P::NC;
   const int b = blockIdx.y;
@@ -425,15 +447,26 @@ __global__ __launch_bounds__(THREADS) void gather_lds_kernel(P p, XF xf, const f
       }
       for (int c = 0; c < g; ++c) {
         const float *row = lds + c * Lp;
+        [[maybe_unused]] float ascale = 1.0f, ashift = 0.0f;   // the addend transform of row c0 + c (uniform)
+        if constexpr (!AX::kPlain) ax.params(c0 + c, ascale, ashift);
         if constexpr (VEC == 4) {
           const float r0 = combine<NC, P::kMaySkip, PAD>(t[0], row, pshift), r1 = combine<NC, P::kMaySkip, PAD>(t[1], row, pshift);
           float r2 = combine<NC, P::kMaySkip, PAD>(t[2], row, pshift), r3 = combine<NC, P::kMaySkip, PAD>(t[3], row, pshift);
           float q0 = r0, q1 = r1;
-          if (add) { const float4 a = ld4(add + (size_t)c * J + j0); q0 = q0 + a.x; q1 = q1 + a.y; r2 = r2 + a.z; r3 = r3 + a.w; }
+          if (add) {
+            float4 a = ld4(add + (size_t)c * J + j0);
+            if constexpr (!AX::kPlain)
+              a = make_float4(ax.apply(a.x, ascale, ashift), ax.apply(a.y, ascale, ashift), ax.apply(a.z, ascale, ashift), ax.apply(a.w, ascale, ashift));
+            q0 = q0 + a.x; q1 = q1 + a.y; r2 = r2 + a.z; r3 = r3 + a.w;
+          }
           st4(out + (size_t)c * J + j0, q0, q1, r2, r3);
         } else {
           float r = combine<NC, P::kMaySkip, PAD>(t[0], row, pshift);
-          if (add) r = r + add[(size_t)c * J + j0];
+          if (add) {
+            float a = add[(size_t)c * J + j0];
+            if constexpr (!AX::kPlain) a = ax.apply(a, ascale, ashift);
+            r = r + a;
+          }
           out[(size_t)c * J + j0] = r;
         }
       }
@@ -452,10 +485,10 @@ __global__ __launch_bounds__(THREADS) void gather_lds_kernel(P p, XF xf, const f
 // compiler's vmcnt waits leave the younger grid in flight -- measured 35.1 vs 35.2 us at (16,64,4096,32): with half the waves the LDS
 // write and gather phases take twice as long, and the fixed part of the launch (one slab per CU alone costs 9 us; eight slabs per
 // workgroup reach 0.69 of the HBM peak where four reach 0.55) is untouched.  Removed.)
-template <class P, class XF>
+template <class P, class XF, class AX = AddPlain>
 __global__ __launch_bounds__(1024) void gather_lds_pipe_kernel(P p, XF xf, const float *__restrict__ src, float *__restrict__ dst,
                                                                int C, int L, int J, int SEQ, int pshift,
-                                                               const float *__restrict__ addend = nullptr) {
+                                                               const float *__restrict__ addend = nullptr, AX ax = AX{}) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int NC = P::NC, THREADS = 1024, kB = 8;
   const int b = blockIdx.y;
@@ -529,6 +562,9 @@ __global__ __launch_bounds__(1024) void gather_lds_pipe_kernel(P p, XF xf, const
     const size_t rowoff = ((size_t)b * C + c) * J;
     const __amdgpu_buffer_rsrc_t arsrc = row_descriptor(addend ? addend : dst, rowoff, addend ? J * 4 : 0);
     const u32x4 add = __builtin_amdgcn_raw_buffer_load_b128(arsrc, voff, 0, 0);
+    // the addend transform of this row: scalar loads (c is uniform), requested here so that they have long returned at the store
+    [[maybe_unused]] float ascale = 1.0f, ashift = 0.0f;
+    if constexpr (!AX::kPlain) ax.params(c, ascale, ashift);
     __builtin_amdgcn_sched_barrier(0);
     if (sq > 0) lds_barrier();                              // every wave is done reading the previous slab
     commit(sq + 1 < SEQ && c + 1 < C, c + 1);               // waits for this slab's loads only; refills the registers as it goes
@@ -546,9 +582,16 @@ __global__ __launch_bounds__(1024) void gather_lds_pipe_kernel(P p, XF xf, const
       p.unpack(pk[h], t);
       r[h] = combine<NC, P::kMaySkip, true>(t, lds, pshift);
     }
-    if (addend) {                                           // (no memory operation in here)
-      r[0] = r[0] + __uint_as_float(add.x); r[1] = r[1] + __uint_as_float(add.y);
-      r[2] = r[2] + __uint_as_float(add.z); r[3] = r[3] + __uint_as_float(add.w);
+    // (a transformed addend is never null -- the launcher's entry requires it: straight-line, so that the transform's arithmetic can be
+    //  scheduled into the gather phase above, the addend quad having arrived long before)
+    if (AX::kPlain ? addend != nullptr : true) {            // (no memory operation in here)
+      float a[4] = {__uint_as_float(add.x), __uint_as_float(add.y), __uint_as_float(add.z), __uint_as_float(add.w)};
+      if constexpr (!AX::kPlain) {
+#pragma unroll
+        for (int h = 0; h < 4; ++h) a[h] = ax.apply(a[h], ascale, ashift);
+      }
+      r[0] = r[0] + a[0]; r[1] = r[1] + a[1];
+      r[2] = r[2] + a[2]; r[3] = r[3] + a[3];
     }
     // uniform row descriptor + the thread's 32-bit byte offset: threads past J are dropped by the bounds check
     const __amdgpu_buffer_rsrc_t drsrc = row_descriptor(dst, rowoff, J * 4);
@@ -572,10 +615,10 @@ __global__ __launch_bounds__(1024) void gather_lds_pipe_kernel(P p, XF xf, const
 // grid loads are in flight together with the coordinate loads.  G = 2 (G = 4 spills ~70 registers at 1024 threads).  Requires L / 4 == 1024:
 // load u of a thread is quad `tid` of row u, so the row transform of load u is that of channel c0 + u.  Same expressions per
 // output element as gather_lds_kernel / gather_lds_pipe_kernel: bit-identical.
-template <class P, class XF, int G>
+template <class P, class XF, int G, class AX = AddPlain>
 __global__ __launch_bounds__(1024) void gather_lds_pipe_rows_kernel(P p, XF xf, const float *__restrict__ src, float *__restrict__ dst,
                                                                 int C, int L, int J, int SEQ, int pshift,
-                                                                const float *__restrict__ addend = nullptr) {
+                                                                const float *__restrict__ addend = nullptr, AX ax = AX{}) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int NC = P::NC, THREADS = 1024;
   const int b = blockIdx.y;
@@ -650,6 +693,13 @@ __global__ __launch_bounds__(1024) void gather_lds_pipe_rows_kernel(P p, XF xf, 
     u32x4 add[G];
 #pragma unroll
     for (int u = 0; u < G; ++u) add[u] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, voff, u * J * 4, 0);
+    // the addend transforms of the slab's rows: scalar loads (uniform channels; a row past C takes the last channel's, its store is dropped)
+    [[maybe_unused]] float ascale[G], ashift[G];
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      ascale[u] = 1.0f; ashift[u] = 0.0f;
+      if constexpr (!AX::kPlain) ax.params(min(c0 + u, C - 1), ascale[u], ashift[u]);
+    }
     __builtin_amdgcn_sched_barrier(0);
     if (sq > 0) lds_barrier();                              // every wave is done reading the previous slab
     commit();                                               // waits for this slab's loads only
@@ -675,9 +725,15 @@ __global__ __launch_bounds__(1024) void gather_lds_pipe_rows_kernel(P p, XF xf, 
     const __amdgpu_buffer_rsrc_t drsrc = row_descriptor(dst, rowoff, rows * J * 4);   // rows past C / threads past J: dropped
 #pragma unroll
     for (int u = 0; u < G; ++u) {
-      if (addend) {                                         // (no memory operation in here)
-        r[u][0] = r[u][0] + __uint_as_float(add[u].x); r[u][1] = r[u][1] + __uint_as_float(add[u].y);
-        r[u][2] = r[u][2] + __uint_as_float(add[u].z); r[u][3] = r[u][3] + __uint_as_float(add[u].w);
+      if (addend) {                                         // (no memory operation in here; a branch also where the addend is transformed:
+                                                            //  straight-line, the transform is hoisted among the gathers and spills 18 registers)
+        float a[4] = {__uint_as_float(add[u].x), __uint_as_float(add[u].y), __uint_as_float(add[u].z), __uint_as_float(add[u].w)};
+        if constexpr (!AX::kPlain) {
+#pragma unroll
+          for (int h = 0; h < 4; ++h) a[h] = ax.apply(a[h], ascale[u], ashift[u]);
+        }
+        r[u][0] = r[u][0] + a[0]; r[u][1] = r[u][1] + a[1];
+        r[u][2] = r[u][2] + a[2]; r[u][3] = r[u][3] + a[3];
       }
       u32x4 o;
       o.x = __float_as_uint(r[u][0]); o.y = __float_as_uint(r[u][1]); o.z = __float_as_uint(r[u][2]); o.w = __float_as_uint(r[u][3]);
@@ -781,10 +837,15 @@ inline int enable_big_lds(K kernel, size_t bytes) {
 
 // vec_ok: J % 4 == 0 and every per-element array (incl. src/dst rows of length J) 16-byte aligned.
 // pshift > 0: rows are voxel grids of resolution 2^pshift; stage them padded (see combine()).
-template <class P, class XF = XfNone>
+template <class P, class XF = XfNone, class AX = AddPlain>
 int launch_gather(const P &p, const float *src, float *dst, int B, int C, int L, int J, bool vec_ok,
-                  hipStream_t s, const char *what, const XF &xf = XF{}, int pshift = 0, const float *addend = nullptr) {
+                  hipStream_t s, const char *what, const XF &xf = XF{}, int pshift = 0, const float *addend = nullptr,
+                  const AX &ax = AX{}) {
   if (B == 0 || C == 0 || J == 0) return 0;
+  if (!AX::kPlain && !addend) {                         // (the kernels add a transformed addend unconditionally)
+    set_error("%s: an addend transform needs an addend", what);
+    return PVCNN_ERR_INVALID_ARGUMENT;
+  }
   if (pshift > 0 && (size_t)(L + (L >> pshift)) * sizeof(float) > (size_t)kLdsBytesPerCU) pshift = 0;   // padding must not cost the LDS path
   SlabPlan pl = plan_slab(B, C, L, pshift);
   if constexpr (P::kGridRows) {
@@ -797,14 +858,14 @@ int launch_gather(const P &p, const float *src, float *dst, int B, int C, int L,
       const int slabs = ceil_div(C, GR);
       const int seq = (int)std::min<long>(8, std::max<long>(1, (long)B * slabs / kNumCU));
       const size_t bytes = (size_t)GR * (L + (L >> pshift)) * sizeof(float);
-      auto k = gather_lds_pipe_rows_kernel<P, XF, GR>;
+      auto k = gather_lds_pipe_rows_kernel<P, XF, GR, AX>;
       if (int e = enable_big_lds(k, bytes)) { set_error("%s: LDS attribute: %d", what, e); return e; }
-      hipLaunchKernelGGL(k, dim3(ceil_div(slabs, seq), B), dim3(1024), bytes, s, p, xf, src, dst, C, L, J, seq, pshift, addend);
+      hipLaunchKernelGGL(k, dim3(ceil_div(slabs, seq), B), dim3(1024), bytes, s, p, xf, src, dst, C, L, J, seq, pshift, addend, ax);
       return check_launch(what);
     }
   }
   if (!pl.lds) {
-    if (!XF::kIdentity || addend) {
+    if (!XF::kIdentity || addend || !AX::kPlain) {
       set_error("%s: row does not fit LDS; the fused transform / addend needs the LDS path", what);
       return PVCNN_ERR_INVALID_ARGUMENT;
     } else if constexpr (XF::kIdentity) {
@@ -819,17 +880,17 @@ int launch_gather(const P &p, const float *src, float *dst, int B, int C, int L,
     // software-pipelined single-row-slab variant (see gather_lds_pipe_kernel); PVCNN_GATHER_PIPE=0 opts out (switches.h)
     if (switches().gather_pipe && pl.threads == 1024 && pl.G == 1 && pshift > 0 && vec_ok && J <= 1024 * 4 && (L & 3) == 0 && (L >> 2) <= 1024 * 8 &&
         aligned16(src) && (((size_t)L * sizeof(float)) & 15) == 0) {
-      auto k = gather_lds_pipe_kernel<P, XF>;
+      auto k = gather_lds_pipe_kernel<P, XF, AX>;
       if (int e = enable_big_lds(k, pl.bytes)) { set_error("%s: LDS attribute: %d", what, e); return e; }
-      hipLaunchKernelGGL(k, grid, dim3(1024), pl.bytes, s, p, xf, src, dst, C, L, J, pl.seq, pshift, addend);
+      hipLaunchKernelGGL(k, grid, dim3(1024), pl.bytes, s, p, xf, src, dst, C, L, J, pl.seq, pshift, addend, ax);
       return check_launch(what);
     }
   }
 #define PVCNN_LAUNCH_GATHER_P(VEC, T, PADV)                                                      \
   do {                                                                                           \
-    auto k = (J <= T * VEC) ? gather_lds_kernel<P, VEC, T, true, XF, PADV> : gather_lds_kernel<P, VEC, T, false, XF, PADV>; \
+    auto k = (J <= T * VEC) ? gather_lds_kernel<P, VEC, T, true, XF, PADV, AX> : gather_lds_kernel<P, VEC, T, false, XF, PADV, AX>; \
     if (int e = enable_big_lds(k, pl.bytes)) { set_error("%s: LDS attribute: %d", what, e); return e; } \
-    hipLaunchKernelGGL(k, grid, dim3(T), pl.bytes, s, p, xf, src, dst, C, L, J, pl.G, pl.seq, pshift, addend); \
+    hipLaunchKernelGGL(k, grid, dim3(T), pl.bytes, s, p, xf, src, dst, C, L, J, pl.G, pl.seq, pshift, addend, ax); \
   } while (0)
 #define PVCNN_LAUNCH_GATHER(VEC, T)                                                              \
   do {                                                                                           \

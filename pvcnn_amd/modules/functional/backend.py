@@ -983,10 +983,15 @@ class HipBackend:
              ws, ws.numel())
         return mean, rstd
 
+    # PVCNN_POINT_FUSED=0 (read once per process): PVConv's point branch through its own BatchNorm + ReLU pass (A/B; fused is the default)
+    has_point_branch_fused = os.environ.get('PVCNN_POINT_FUSED', '1') != '0'
+
     def trilinear_devoxelize_bnact_forward(self, r, is_training, coords, features, gamma, beta, mean, rstd, slope, addend=None,
-                                           se_scale=None):
+                                           se_scale=None, addend_bn=None):
         """trilinear_devoxelize_forward of leaky_relu(bn(features)) [* se_scale (B,C): SE3d's excitation] without materialising that
-        tensor: features (B,C,R^3) is the PRE-BatchNorm grid, mean / rstd (C) its statistics."""
+        tensor: features (B,C,R^3) is the PRE-BatchNorm grid, mean / rstd (C) its statistics.
+        addend_bn = (gamma | None, beta | None, mean, rstd, slope): the addend is PRE-BatchNorm too (PVConv's point branch behind its
+        1x1 convolution); its BatchNorm + ReLU | LeakyReLU(slope) is applied where the gather's store adds it (no se_scale then)."""
         _f32(features, 'features'); _f32(coords, 'coords')
         r = int(r)
         _shape(features.dim() == 3 and coords.dim() == 3 and coords.shape[1] == 3
@@ -1007,6 +1012,20 @@ class HipBackend:
             wgts = torch.empty((b, 8, n), dtype=torch.float32, device=dev)
         else:
             inds, wgts = _dummies(dev)
+        if addend_bn is not None:
+            if addend is None or se_scale is not None or len(addend_bn) != 5:
+                raise RuntimeError('trilinear_devoxelize: addend_bn = (gamma, beta, mean, rstd, slope) goes with an addend and without se_scale')
+            a_gamma, a_beta, a_mean, a_rstd, a_slope = addend_bn
+            for name, t, optional in (('gamma', a_gamma, True), ('beta', a_beta, True), ('mean', a_mean, False), ('rstd', a_rstd, False)):
+                if t is None and optional:
+                    continue
+                _f32(t, 'addend_bn ' + name)
+                if tuple(t.shape) != (c,) or not t.is_contiguous():
+                    raise RuntimeError(f'trilinear_devoxelize: addend_bn {name} (C,) contiguous expected')
+            _run(self.lib.pvcnn_trilinear_devox_bnact_addbn_fwd, 'trilinear_devoxelize_bnact_forward', features, coords, features, gamma,
+                 beta, mean, rstd, float(slope), b, c, n, r, int(bool(is_training)), inds if is_training else None,
+                 wgts if is_training else None, addend, a_gamma, a_beta, a_mean, a_rstd, float(a_slope), outs)
+            return [outs, inds, wgts]
         _run(self.lib.pvcnn_trilinear_devox_bnact_fwd, 'trilinear_devoxelize_bnact_forward', features, coords, features, gamma, beta,
              mean, rstd, float(slope), b, c, n, r, int(bool(is_training)), inds if is_training else None,
              wgts if is_training else None, addend, se_scale, outs)

@@ -91,7 +91,8 @@ def _statistics(x3, use_batch_stats, stats_part, stats_shift, running_mean, runn
     return running_mean.contiguous(), torch.rsqrt(running_var + eps)
 
 
-__all__ = ['batch_norm_act', 'batch_norm_act_devoxelize', 'batch_norm_act_se_devoxelize', 'fusable_tail', 'run_layers', 'fused_dropout_ok',
+__all__ = ['batch_norm_act', 'batch_norm_act_devoxelize', 'batch_norm_act_se_devoxelize', 'batch_norm_act_devoxelize_point_bn',
+           'point_bn_fusable', 'fusable_tail', 'run_layers', 'fused_dropout_ok',
            'folded_parameters', 'folded_snapshot']
 
 
@@ -272,6 +273,79 @@ def batch_norm_act_devoxelize(grid, coords, bn, slope, resolution, is_training, 
     use_batch_stats, momentum, rm, rv, counter, part, shift = _module_call(bn, stats_part)
     return BatchNormActDevoxelize.apply(grid, coords, bn.weight, bn.bias, rm, rv, use_batch_stats, momentum, bn.eps, slope,
                                         resolution, is_training, part, shift, addend, counter)
+
+
+class BatchNormActDevoxelizePointBN(Function):
+    """trilinear_devoxelize(leaky_relu(batch_norm(grid)), coords) + act(batch_norm1d(pre)): BatchNormActDevoxelize with the addend --
+    PVConv's point branch (modules/pvconv.py:31-34,38) -- handed over PRE-BatchNorm, as its 1x1 convolution wrote it.  The gather
+    applies the point branch's BatchNorm + ReLU | LeakyReLU to the addend quad it adds in its store (csrc/slab.h, AddBnAct), so the
+    activated point branch is neither written nor read: one pass over (B, C, N) less per PVConv.  Training mode only (both
+    BatchNorms on batch statistics finalised from their convolutions' epilogue sums).  Bit-identical to batch_norm_act on `pre`
+    followed by BatchNormActDevoxelize with the result as addend, forward and backward: the backward runs the very passes of the two
+    nodes it replaces (the gather's gradient IS the activated addend's)."""
+
+    @staticmethod
+    @amp_fwd
+    def forward(ctx, grid, coords, weight, bias, running_mean, running_var, momentum, eps, slope, resolution, stats_part, stats_shift,
+                counter, pre, p_weight, p_bias, p_running_mean, p_running_var, p_momentum, p_eps, p_slope, p_stats_part, p_stats_shift,
+                p_counter):
+        shape, x3, w, b = _prologue(grid, weight, bias)
+        p_shape, pre3, pw, pb = _prologue(pre, p_weight, p_bias)
+        p_mean, p_rstd = _statistics(pre3, True, p_stats_part, p_stats_shift, p_running_mean, p_running_var, p_momentum, p_eps, p_counter)
+        mean, rstd = _statistics(x3, True, stats_part, stats_shift, running_mean, running_var, momentum, eps, counter)
+        r = int(resolution)
+        pts = coords.contiguous()
+        taps = CornerTaps.of(coords, r)
+        out = taps.forward(lambda emit: native().trilinear_devoxelize_bnact_forward(
+            r, emit, pts, x3, w, b, mean, rstd, slope, pre3, addend_bn=(pw, pb, p_mean, p_rstd, p_slope)))
+        ctx.save_for_backward(x3, w, b, mean, rstd, pre3, pw, pb, p_mean, p_rstd, taps.inds, taps.wgts)
+        ctx.taps = taps
+        ctx.slope, ctx.shape, ctx.p_slope, ctx.p_shape = slope, shape, p_slope, p_shape
+        return out
+
+    @staticmethod
+    @amp_bwd
+    def backward(ctx, grad_out):
+        x3, w, b, mean, rstd, pre3, pw, pb, p_mean, p_rstd, _, _ = ctx.saved_tensors
+        g_rows = _rows(grad_out, grad_out.shape)
+        g_act = ctx.taps.backward(g_rows)
+        gx, gw, gb = _bnact_backward(x3, g_act.view(x3.shape), w, b, mean, rstd, ctx.slope, True, ctx.shape)
+        gp, gpw, gpb = _bnact_backward(pre3, g_rows, pw, pb, p_mean, p_rstd, ctx.p_slope, True, ctx.p_shape)
+        return ((gx, None, gw if w is not None else None, gb if b is not None else None) + (None,) * 9
+                + (gp, gpw if pw is not None else None, gpb if pb is not None else None) + (None,) * 8)
+
+
+def point_bn_fusable(point_layers, features, training):
+    """Can PVConv's point branch `point_layers` = [1x1 convolution, BatchNorm, ReLU | LeakyReLU] hand its PRE-BatchNorm tensor to the
+    devoxelize gather (batch_norm_act_devoxelize_point_bn)?  -> (conv, bn, slope) | None.  Needs: exactly that stack with nothing
+    hooked, training mode on batch statistics, fp32 point features (B, C, N) on the GPU, no autocast, gradients enabled, no folded
+    snapshot on the convolution, and the backend's capability flag (PVCNN_POINT_FUSED)."""
+    be = native()
+    if not (training and getattr(be, 'has_point_branch_fused', False) and getattr(be, 'has_pwconv', False)
+            and getattr(be, 'has_bnact', False)):
+        return None
+    mods = list(point_layers)
+    if len(mods) != 3 or _has_hooks(point_layers) or any(_has_hooks(m) for m in mods):
+        return None
+    conv, bn, act = mods
+    if not (_is_pointwise(conv) and isinstance(conv, nn.Conv1d) and isinstance(bn, nn.BatchNorm1d) and _slope(act) is not None):
+        return None
+    if not (bn.training and conv.weight.dtype == torch.float32 and getattr(conv, _fold.ATTR, None) is None):
+        return None
+    if not (features.is_cuda and features.dtype == torch.float32 and features.dim() == 3 and features.numel() > 0
+            and not torch.is_autocast_enabled() and torch.is_grad_enabled()):
+        return None
+    return conv, bn, _slope(act)
+
+
+def batch_norm_act_devoxelize_point_bn(grid, coords, bn, slope, resolution, stats_part, pre, p_bn, p_slope, p_stats_part):
+    """trilinear_devoxelize(act(bn(grid)), coords) + act(p_bn(pre)): PVConv's tail with the point branch's BatchNorm + activation applied
+    in the gather's store; `pre` (B, C, N) is the point branch's 1x1 convolution output, p_stats_part its epilogue sums (training mode)."""
+    _, momentum, rm, rv, counter, part, shift = _module_call(bn, stats_part)
+    _, p_momentum, p_rm, p_rv, p_counter, p_part, p_shift = _module_call(p_bn, p_stats_part)
+    return BatchNormActDevoxelizePointBN.apply(grid, coords, bn.weight, bn.bias, rm, rv, momentum, bn.eps, slope, resolution, part, shift,
+                                               counter, pre, p_bn.weight, p_bn.bias, p_rm, p_rv, p_momentum, p_bn.eps, p_slope, p_part,
+                                               p_shift, p_counter)
 
 
 def _se_excite_forward(sums, gamma, beta, w1, w2, s3):

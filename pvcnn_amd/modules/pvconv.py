@@ -13,7 +13,8 @@ import torch.nn as nn
 
 from . import functional as F
 from .functional._autograd import native
-from .functional.bnact import batch_norm_act_devoxelize, batch_norm_act_se_devoxelize, fusable_tail, run_layers
+from .functional.bnact import (batch_norm_act_devoxelize, batch_norm_act_devoxelize_point_bn, batch_norm_act_se_devoxelize, fusable_tail,
+                               point_bn_fusable, run_layers, _has_hooks)
 from .functional.conv3d import conv_nsplit, voxel_conv3d
 from .se import SE3d
 from .shared_mlp import SharedMLP
@@ -67,6 +68,17 @@ class PVConv(nn.Module):
         self.voxel_layers = nn.Sequential(*grid_ops)
         self.point_features = SharedMLP(in_channels, out_channels)
 
+    def _point_branch_in_gather(self, features, bn, se):
+        """-> (the point branch's BatchNorm, its activation's slope) when the fused tail's gather can apply them to its addend
+        (functional.bnact.point_bn_fusable: training mode, a plain [1x1 conv, BatchNorm1d, ReLU] SharedMLP with nothing hooked, fp32
+        on the GPU without autocast), else None.  PVConvs with squeeze-and-excitation keep the separate pass."""
+        if se is not None or not (self.training and bn.training) or not isinstance(self.point_features, SharedMLP):
+            return None
+        if _has_hooks(self.point_features):              # (a hooked SharedMLP goes through its own __call__)
+            return None
+        found = point_bn_fusable(self.point_features.layers, features, self.training)
+        return None if found is None else found[1:]
+
     def forward(self, inputs):
         features, coords = inputs
         grid, grid_coords = self.voxelization(features, coords)
@@ -78,6 +90,14 @@ class PVConv(nn.Module):
             bn, slope, se = tail
             ntail = 2 if se is None else 3
             grid, stats_part = run_layers(self.voxel_layers, grid, stop=len(self.voxel_layers) - ntail, tail_stats=True)
+            point = self._point_branch_in_gather(features, bn, se)
+            if point is not None:
+                # ... and the point branch's own BatchNorm + ReLU: the gather takes the 1x1 convolution's output as its addend and
+                # normalises and activates the quad it adds -- the activated point branch is never written either
+                p_bn, p_slope = point
+                pre, p_stats = run_layers(self.point_features.layers, features, stop=1, tail_stats=True)
+                return batch_norm_act_devoxelize_point_bn(grid, grid_coords, bn, slope, self.resolution, stats_part,
+                                                          pre, p_bn, p_slope, p_stats), coords
             per_point = self.point_features(features)
             # ... and so does the sum with the point branch: added in the gather's store (one rounded addition, like the
             # reference's `voxel_features + point_features`, modules/pvconv.py:38)
