@@ -648,6 +648,44 @@ PVCNN_API int pvcnn_dense_bn_relu_bwd(const float *x, const float *grad_y, const
  * schedule (train.py:121-122: scheduler.step()) reaches launches that were captured into a hipGraph. */
 PVCNN_API int pvcnn_adam_step(float *p, const float *g, float *m, float *v, size_t n, float *step, const float *hyper, int inc_step,
                     void *stream);
+/* Additions without a version step (nothing existing changes): parameter groups, AdamW, amsgrad and a global gradient norm with a
+ * clip coefficient and a skip guard, all on the device -- nothing is allocated, nothing is read back, every launch is capturable.
+ *
+ * The STATUS BLOCK: 8 floats in device memory (4-byte aligned), owned by the caller.
+ *   [0] norm     (written by pvcnn_grad_norm_finalize)  L2 norm over everything the partials covered, before clipping
+ *   [1] coef     (written)  min(1, max_norm / (norm + 1e-6)): torch.nn.utils.clip_grad_norm_'s coefficient
+ *   [2] skip     (written)  1.0 when the sum of squares is not finite AND [5] != 0, else 0.0
+ *   [3] skipped  (updated)  += 1.0 with every finalize that sets [2]; the caller zeroes it once
+ *   [4] max_norm (read)     written by the caller (a schedule may move it between replays of a graph); +inf = no clipping
+ *   [5] skip_nonfinite (read)  != 0 enables the skip flag
+ *   [6], [7] reserved, never touched.
+ *
+ * pvcnn_grad_sqsum: partials[0 .. nparts) = sums of g[i]^2 over the n floats of one buffer (g 16-byte aligned), one per workgroup of a
+ *   grid of nparts (1 ... 65535) workgroups: the caller fixes the grid and with it the order of every addition.  Each lane adds
+ *   its squares in index order in fp32; lane totals, waves and workgroups are added in fp64 and the partial is rounded to fp32 once.
+ *   n == 0 writes zeros.  Writes partials only.
+ * pvcnn_grad_norm_finalize: one workgroup adds partials[0 .. nparts) -- the partials of ALL buffers of an optimizer step, laid out
+ *   back to back by the caller -- in a fixed order in fp64 and writes status[0 .. 3] as above (reads [4], [5]).  No atomics: two runs
+ *   on the same gradients give the same bits.
+ * pvcnn_adam_step_grouped: pvcnn_adam_step for a buffer that holds parameters of several GROUPS, ONE launch for the buffer.
+ *   hyper: (ngroups, 5) floats in device memory, lr, beta1, beta2, eps, weight_decay per group (1 <= ngroups <= 256).
+ *   runs:  nruns (1 ... 4096) int32 pairs (end offset, group id) in device memory (4-byte aligned): run r covers the elements
+ *          [end[r-1], end[r]) (end[-1] = 0); ends strictly increasing, the last one == n (hence n < 2^31); a group boundary may fall on
+ *          any element.  A group id outside [0, ngroups) is clamped into it.
+ *   vmax:  NULL, or the amsgrad buffer max_exp_avg_sq (n floats, 16-byte aligned, updated in place: vmax = max(vmax, v), and used
+ *          in the denominator in v's place).
+ *   decoupled != 0: torch.optim.AdamW's order -- p *= 1 - lr * weight_decay, then Adam on the bare gradient -- instead of
+ *          g += weight_decay * p.  vmax and decoupled hold for the whole launch, not per group.
+ *   status: NULL, or a status block as above: the gradient is multiplied by status[1] in registers (g itself is only read) before
+ *          the weight decay -- the order clip_grad_norm_ followed by step() gives -- and with status[2] != 0 the launch writes
+ *          NOTHING and inc_step does not increment the counter.
+ *   p, g, m, v 16-byte aligned; step, inc_step as for pvcnn_adam_step.  With every group holding the same hyper-parameters, vmax and
+ *   status NULL and decoupled 0, p / m / v come out bit-identical to pvcnn_adam_step's. */
+PVCNN_API int pvcnn_grad_sqsum(const float *g, size_t n, float *partials, int nparts, void *stream);
+PVCNN_API int pvcnn_grad_norm_finalize(const float *partials, int nparts, float *status, void *stream);
+PVCNN_API int pvcnn_adam_step_grouped(float *p, const float *g, float *m, float *v, float *vmax, size_t n, float *step,
+                                      const float *hyper, int ngroups, const int *runs, int nruns, const float *status,
+                                      int decoupled, int inc_step, void *stream);
 
 /* ---- (ABI v13) evaluation on the device (csrc/evaluate.hip): evaluate/s3dis/eval.py:139-216, evaluate/shapenet/eval.py:124-200,
  * meters/s3dis.py, meters/shapenet.py.  Integer atomics only: every output is bitwise deterministic.  Index arrays are int64 (what

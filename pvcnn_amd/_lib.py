@@ -122,6 +122,9 @@ SIGNATURES = {
     'pvcnn_dense_bn_relu_fwd': (_i, [_vp] * 8 + [_i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     'pvcnn_dense_bn_relu_bwd': (_i, [_vp] * 7 + [_i, _i, _i] + [_vp] * 6),
     'pvcnn_adam_step': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _vp]),
+    'pvcnn_grad_sqsum': (_i, [_vp, _sz, _vp, _i, _vp]),
+    'pvcnn_grad_norm_finalize': (_i, [_vp, _i, _vp, _vp]),
+    'pvcnn_adam_step_grouped': (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
     'pvcnn_trilinear_devox_bwd_strided': (_i, [_vp, ctypes.c_long, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'pvcnn_eval_tile': (_i, [_vp, _ll, _ll, _ll, _ll, _vp, _i, _i, _i, _i, _vp, _vp]),
     'pvcnn_vote_confidence': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
