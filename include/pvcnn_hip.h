@@ -888,6 +888,38 @@ PVCNN_API int pvcnn_kitti_ap_stats(const double *overlaps, const long long *gt_o
                                    int num_min_overlaps, const double *thresholds, const int *counts, int metric, int compute_aos,
                                    double *pr, void *workspace, size_t workspace_bytes, void *stream);
 
+/* The segmentation criterion: torch.nn.functional.cross_entropy(x, target, weight, ignore_index, reduction, label_smoothing) for
+ * reduction mean / sum, and its gradient, in three launches (an additive group: the ABI version does not move).
+ *   x       fp32 (B, C, S): the S positions of a class row contiguous, class stride S, batch stride x_bstride >= C * S elements
+ *           (a channel slice of a wider tensor is fine);
+ *   target  int64 (B, S): rows contiguous, batch stride t_bstride >= S elements.  A point whose target is ignore_index adds nothing
+ *           to the loss and gets a zero gradient.  A target outside [0, C) that is not ignore_index is handled the same way and is
+ *           counted; it is never used as an index (torch asserts on the device instead);
+ *   weight  fp32 (C) or NULL;
+ *   workspace  pvcnn_xent_workspace_bytes(B, S) bytes, 16-byte aligned, written by the two forward launches and read by the
+ *           backward one: [denominator, sum of the weights, 0, 0] fp32 | 5 x pvcnn_xent_parts(B, S) fp64 per-workgroup partial sums
+ *           (nll numerator, sum of log-sum-exp, weight denominator, out-of-range count, weighted logit sum) | (max, sum of exp) fp32
+ *           per point.  weight must be packed (element stride 1).
+ *           Both queries are host-only and return 0 for sizes the kernels refuse.
+ * pvcnn_xent_partials: the per-point (max, sum of exp) and the per-workgroup partial sums (smoothing != 0: the smoothing numerator
+ *   too).  pvcnn_xent_finalize: one workgroup adds the partials in a fixed order in fp64; loss[0] = [(1 - label_smoothing) nll +
+ *   label_smoothing / C smooth] / denominator (mean != 0; every point ignored: NaN, as torch) or the numerator (mean == 0);
+ *   bad_targets (one int64 in device memory, or NULL) += the out-of-range count, a plain read-modify-write by one
+ *   thread: calls that run concurrently (different streams) must not share a counter.  pvcnn_xent_bwd: grad_x (B, C, S) contiguous,
+ *   every element written, = grad_out[0] (one fp32 in device memory, read on the device) / denominator * [(1 - eps) w_t (p_j - [j == t])
+ *   + eps / C (W p_j - w_j)] (mean == 0: without the division).  The same arguments must go to all three; a bad value is refused before any
+ *   pointer is looked at.  Deterministic: no float
+ *   atomics, the same bits for the same inputs. */
+PVCNN_API size_t pvcnn_xent_parts(long long B, long long S);
+PVCNN_API size_t pvcnn_xent_workspace_bytes(long long B, long long S);
+PVCNN_API int pvcnn_xent_partials(const float *x, long long x_bstride, const long long *target, long long t_bstride, const float *weight,
+                                  long long B, int C, long long S, long long ignore_index, int smoothing, void *workspace, void *stream);
+PVCNN_API int pvcnn_xent_finalize(const float *weight, long long B, int C, long long S, double label_smoothing, int mean, void *workspace,
+                                  float *loss, long long *bad_targets, void *stream);
+PVCNN_API int pvcnn_xent_bwd(const float *x, long long x_bstride, const long long *target, long long t_bstride, const float *weight,
+                             const float *grad_out, long long B, int C, long long S, long long ignore_index, float label_smoothing,
+                             int mean, const void *workspace, float *grad_x, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -162,6 +162,12 @@ SIGNATURES = {
     'pvcnn_pwconv_fwd_split_act': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _vp]),
     'pvcnn_pwconv_fwd_act': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _f, _vp, _i, _vp]),
     'pvcnn_kitti_ap_stats': (_i, [_vp] * 5 + [_ll, _ll, _ll, _i, _i] + [_vp] * 9 + [_i, _i, _i] + [_vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    # the cross-entropy criterion (csrc/xent.hip): two forward launches, one backward
+    'pvcnn_xent_parts': (_sz, [_ll, _ll]),
+    'pvcnn_xent_workspace_bytes': (_sz, [_ll, _ll]),
+    'pvcnn_xent_partials': (_i, [_vp, _ll, _vp, _ll, _vp, _ll, _i, _ll, _ll, _i, _vp, _vp]),
+    'pvcnn_xent_finalize': (_i, [_vp, _ll, _i, _ll, _d, _i, _vp, _vp, _vp, _vp]),
+    'pvcnn_xent_bwd': (_i, [_vp, _ll, _vp, _ll, _vp, _vp, _ll, _i, _ll, _ll, _f, _i, _vp, _vp, _vp]),
 }
 
 _lib = None
