@@ -920,6 +920,43 @@ PVCNN_API int pvcnn_xent_bwd(const float *x, long long x_bstride, const long lon
                              const float *grad_out, long long B, int C, long long S, long long ignore_index, float label_smoothing,
                              int mean, const void *workspace, float *grad_x, void *stream);
 
+/* The deep-mutual-learning criterion (csrc/dml.hip; an additive group: the ABI version does not move).  a / x and b / y are fp32
+ * (B, C, S) logits laid out like pvcnn_xent_*'s x (batch strides >= C * S elements, no alignment requirement); target, weight,
+ * ignore_index, out-of-range targets, grad_out (one fp32 in device memory) and bad_targets are pvcnn_xent_*'s too.  With
+ * p = softmax(a), q = softmax(b) per point, log p formed as (a_c - max a) - log(sum exp) so that p_c = 0 gives a zero term, not NaN:
+ *
+ * KL alone -- the reference's kl_loss(x, y):  loss[0] = sum_points sum_c p_c (log p_c - log q_c) / (B S) with p from x, q from y;
+ *   pvcnn_kl_bwd writes grad_y (B, C, S) contiguous, every element, = grad_out[0] (q_j - p_j) / (B S).  x has no gradient.
+ *   workspace  pvcnn_kl_workspace_bytes(B, S) = 16 + 16 B S + 8 pvcnn_xent_parts(B, S) bytes, 16-byte aligned:
+ *           [0, 1 / (B S), 0, 0] fp32 | (max x, sum exp x, max y, sum exp y) fp32 per point | fp64 per-workgroup partial sums.
+ * Pair -- the four terms of a DML step from one pass over both tensors:
+ *   loss[0] = cross_entropy(a, target, weight, ignore_index, mean) + KL(q || p) / (B S)     (the first network's loss)
+ *   loss[1] = cross_entropy(b, target, weight, ignore_index, mean) + KL(p || q) / (B S)     (the student's)
+ *   The KL terms take every point, ignored ones too; the cross-entropy terms skip (and, out of range, count) what pvcnn_xent_*
+ *   skips.  Every point ignored: both losses NaN (0 / 0), the gradients hold the KL part alone.
+ *   pvcnn_dml_pair_bwd writes the gradient of loss[side] for ITS network (side 0: a, side 1: b; the other network is a constant
+ *   of that loss), (B, C, S) contiguous, every element: grad_out[0] [w_t (x_p_j - [j == t]) / den + (x_p_j - other_p_j) / (B S)],
+ *   the first term only for a live point.  a and b go in the same order to all three launches.
+ *   workspace  pvcnn_dml_pair_workspace_bytes(B, S) = 16 + 16 B S + 48 pvcnn_xent_parts(B, S) bytes, 16-byte aligned:
+ *           [den, 1 / (B S), 0, 0] fp32 | (max a, sum exp a, max b, sum exp b) per point | 6 x parts fp64 (nll a, nll b, den,
+ *           out-of-range count, KL(q || p), KL(p || q)).
+ * Both size queries are host-only and return 0 for sizes the kernels do not index.  A bad value is refused (-1, no launch) before
+ * any pointer is looked at.  Deterministic: no float atomics, the same bits for the same inputs. */
+PVCNN_API size_t pvcnn_kl_workspace_bytes(long long B, long long S);
+PVCNN_API int pvcnn_kl_partials(const float *x, long long x_bstride, const float *y, long long y_bstride, long long B, int C, long long S,
+                                void *workspace, void *stream);
+PVCNN_API int pvcnn_kl_finalize(long long B, int C, long long S, void *workspace, float *loss, void *stream);
+PVCNN_API int pvcnn_kl_bwd(const float *x, long long x_bstride, const float *y, long long y_bstride, const float *grad_out, long long B,
+                           int C, long long S, const void *workspace, float *grad_y, void *stream);
+PVCNN_API size_t pvcnn_dml_pair_workspace_bytes(long long B, long long S);
+PVCNN_API int pvcnn_dml_pair_partials(const float *a, long long a_bstride, const float *b, long long b_bstride, const long long *target,
+                                      long long t_bstride, const float *weight, long long B, int C, long long S, long long ignore_index,
+                                      void *workspace, void *stream);
+PVCNN_API int pvcnn_dml_pair_finalize(long long B, int C, long long S, void *workspace, float *loss, long long *bad_targets, void *stream);
+PVCNN_API int pvcnn_dml_pair_bwd(const float *a, long long a_bstride, const float *b, long long b_bstride, const long long *target,
+                                 long long t_bstride, const float *weight, const float *grad_out, long long B, int C, long long S,
+                                 long long ignore_index, int side, const void *workspace, float *grad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

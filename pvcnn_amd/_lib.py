@@ -168,6 +168,15 @@ SIGNATURES = {
     'pvcnn_xent_partials': (_i, [_vp, _ll, _vp, _ll, _vp, _ll, _i, _ll, _ll, _i, _vp, _vp]),
     'pvcnn_xent_finalize': (_i, [_vp, _ll, _i, _ll, _d, _i, _vp, _vp, _vp, _vp]),
     'pvcnn_xent_bwd': (_i, [_vp, _ll, _vp, _ll, _vp, _vp, _ll, _i, _ll, _ll, _f, _i, _vp, _vp, _vp]),
+    # the deep-mutual-learning criterion (csrc/dml.hip): kl_loss alone, and the four terms of a DML step as a pair
+    'pvcnn_kl_workspace_bytes': (_sz, [_ll, _ll]),
+    'pvcnn_kl_partials': (_i, [_vp, _ll, _vp, _ll, _ll, _i, _ll, _vp, _vp]),
+    'pvcnn_kl_finalize': (_i, [_ll, _i, _ll, _vp, _vp, _vp]),
+    'pvcnn_kl_bwd': (_i, [_vp, _ll, _vp, _ll, _vp, _ll, _i, _ll, _vp, _vp, _vp]),
+    'pvcnn_dml_pair_workspace_bytes': (_sz, [_ll, _ll]),
+    'pvcnn_dml_pair_partials': (_i, [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _ll, _ll, _vp, _vp]),
+    'pvcnn_dml_pair_finalize': (_i, [_ll, _i, _ll, _vp, _vp, _vp, _vp]),
+    'pvcnn_dml_pair_bwd': (_i, [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _ll, _i, _ll, _ll, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -18,35 +18,12 @@
 //
 // Deterministic: no float atomics, no ticket fold.  A workgroup adds its lanes' fp64 sums by a fixed butterfly, the one-workgroup
 // finalize adds the per-workgroup partials in a fixed order in fp64.  Every word of every output is written; nothing is memset.
-#include "common.h"
+#include "xent_sums.h"
 
 namespace pvcnn {
 
-constexpr int kXentThreads = 256;
-constexpr int kXentMaxParts = 1024;            // grid cap of the partials launch: beyond 1024 * 256 points the lanes stride
-constexpr int kXentBwdMaxBlocks = 4096;        // grid.x cap of the gradient launch (grid.y walks the classes)
-constexpr int kXentBwdMaxClassRows = 32;
 constexpr size_t kXentStateBytes = 16;         // workspace: [den, W, -, -] floats | kXentSums x parts doubles | (m, s) per point
 constexpr int kXentSums = 5;
-
-__host__ __device__ inline long long xent_parts(long long B, long long S) {
-  const long long blocks = (B * S + kXentThreads - 1) / kXentThreads;
-  return blocks < kXentMaxParts ? blocks : kXentMaxParts;
-}
-
-// the sums of K per-lane values over the workgroup, in every thread (wave butterfly, then the four wave totals in wave order)
-template <int K>
-__device__ __forceinline__ void xent_block_sums(double (&v)[K]) {
-  __shared__ double s_wave[K][kXentThreads / kWave];
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-    if ((threadIdx.x & 63) == 0) s_wave[k][threadIdx.x >> 6] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = ((s_wave[k][0] + s_wave[k][1]) + s_wave[k][2]) + s_wave[k][3];
-}
 
 // parts[k * gridDim.x + workgroup], k = 0: sum nll_i, 1: sum of logf(s_i), 2: sum w_t, 3: number of out-of-range targets,
 // 4: sum_i sum_c w_c (x_c - m) -- 1 and 4 over the live points, with label smoothing only (else 0);
@@ -146,10 +123,6 @@ __global__ __launch_bounds__(kXentThreads) void xent_bwd_kernel(const float *__r
       gp[(size_t)c * (size_t)S] = g;
     }
   }
-}
-
-static bool xent_sizes_ok(long long B, int C, long long S) {
-  return B > 0 && C > 0 && S > 0 && B <= (1ll << 40) / S && (long long)C <= (1ll << 46) / (B * S);
 }
 
 }  // namespace pvcnn

@@ -1,15 +1,15 @@
 """Host-side mirror of the reference's `modules` package (modules/__init__.py:1-8): the same
 ten public classes with the same constructor / forward signatures and sub-module names
 (state_dict keys), implemented over the gfx950 native backend; CrossEntropyLoss (nn.CrossEntropyLoss on the fused criterion)
-is this package's own."""
+and DMLPairLoss (the criterion pair of a deep-mutual-learning step) are this package's own."""
 from .ball_query import BallQuery
 from .frustum import FrustumPointNetLoss
-from .loss import CrossEntropyLoss, KLLoss
+from .loss import CrossEntropyLoss, DMLPairLoss, KLLoss
 from .pointnet import PointNetAModule, PointNetSAModule, PointNetFPModule
 from .pvconv import PVConv
 from .se import SE3d
 from .shared_mlp import SharedMLP
 from .voxelization import Voxelization
 
-__all__ = ['BallQuery', 'CrossEntropyLoss', 'FrustumPointNetLoss', 'KLLoss', 'PointNetAModule', 'PointNetSAModule',
+__all__ = ['BallQuery', 'CrossEntropyLoss', 'DMLPairLoss', 'FrustumPointNetLoss', 'KLLoss', 'PointNetAModule', 'PointNetSAModule',
            'PointNetFPModule', 'PVConv', 'SE3d', 'SharedMLP', 'Voxelization']

@@ -1,11 +1,12 @@
-"""KLLoss module (reference: modules/loss.py:6-9) and CrossEntropyLoss, nn.CrossEntropyLoss on the fused criterion."""
+"""KLLoss module (reference: modules/loss.py:6-9; fused through F.kl_loss), CrossEntropyLoss, nn.CrossEntropyLoss on the fused
+criterion, and DMLPairLoss, the two losses of a deep-mutual-learning step from one pass over both networks' logits."""
 import torch
 import torch.nn as nn
 
 from . import functional as F
-from .functional.loss import _cross_entropy
+from .functional.loss import _cross_entropy, _dml_pair_loss
 
-__all__ = ['KLLoss', 'CrossEntropyLoss']
+__all__ = ['KLLoss', 'CrossEntropyLoss', 'DMLPairLoss']
 
 
 class KLLoss(nn.Module):
@@ -44,3 +45,35 @@ class CrossEntropyLoss(nn.CrossEntropyLoss):
                 self.bad_targets = torch.zeros((), dtype=torch.int64, device=input.device)
             counter = self.bad_targets
         return _cross_entropy(input, target, self.weight, self.ignore_index, self.reduction, self.label_smoothing, counter, fused)
+
+
+class DMLPairLoss(nn.Module):
+    """The criterion pair of a deep-mutual-learning step (reference: train_dml.py:125-137):
+    forward(outputs, outputs_student, targets) -> (loss, loss_student) =
+    (criterion(outputs, targets) + KLLoss()(outputs_student, outputs), criterion(outputs_student, targets) + KLLoss()(outputs, outputs_student)).
+
+    `criterion`: an nn.CrossEntropyLoss or modules.CrossEntropyLoss (None: the default one); its weight, ignore_index, reduction
+    and label_smoothing are taken over.  With reduction 'mean' and no smoothing, on device logits, the four terms are
+    F.dml_pair_loss's two forward launches and one backward launch per network; the two losses are separate autograd nodes, so
+    `loss.backward(); optimizer.step(); loss_student.backward()` and `(loss + loss_student).backward()` both work.  Anything else
+    is composed of F.cross_entropy and F.kl_loss.
+
+    `bad_targets`: as CrossEntropyLoss's -- created on the first call that runs a fused cross entropy, counted once per call."""
+
+    def __init__(self, criterion=None):
+        super().__init__()
+        self.criterion = CrossEntropyLoss() if criterion is None else CrossEntropyLoss.from_torch(criterion)
+        self.bad_targets = None
+
+    def forward(self, outputs, outputs_student, targets):
+        c = self.criterion
+        fused = F.dml_pair_loss_is_fused(outputs, outputs_student, targets, c.weight, c.ignore_index, c.reduction, c.label_smoothing)
+        counter = None
+        if fused or F.cross_entropy_is_fused(outputs, targets, c.weight, c.reduction):
+            if self.bad_targets is None or self.bad_targets.device != outputs.device:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError('DMLPairLoss: call the criterion once before capturing it (its bad_targets counter is '
+                                       'created on the first call; GraphedTrainStep\'s warm-up steps do that)')
+                self.bad_targets = torch.zeros((), dtype=torch.int64, device=outputs.device)
+            counter = self.bad_targets
+        return _dml_pair_loss(outputs, outputs_student, targets, c.weight, c.ignore_index, c.reduction, c.label_smoothing, counter, fused)

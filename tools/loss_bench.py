@@ -10,7 +10,14 @@ only where every one of its rounds beats every one of torch's by more than that 
     with the launches per forward + backward: the kernels torch.profiler sees on the device, and for the fused criterion also the
     native calls through backend._run;
   * the cfg2 training step (PVCNN 1xC, B=16, N=4096, FlatAdam) replayed from its graph with each criterion inside.
-One JSON line per measurement."""
+One JSON line per measurement.
+
+    python tools/loss_bench.py --dml [--dml-iters 2000] [--rounds 3]
+
+The four terms of a deep-mutual-learning step (train_dml.py:125-137) at the recipe's shape, S3DIS B=16, C=13, N=4096, forward + both
+backwards: (a) as before csrc/dml.hip -- modules.CrossEntropyLoss twice plus the torch kl_loss twice, in a fresh child process started
+with PVCNN_FUSED_DML=0 -- against (b) modules.DMLPairLoss on the pair kernels in this process.  Both processes stay up and take their
+rounds in turn (a, b, a, b, ...), each round replayed from a captured graph and issued eagerly, with the launches per pass."""
 import argparse
 import copy
 import json
@@ -62,17 +69,19 @@ def device_kernels(fn):
 
 
 def native_calls(fn):
+    from pvcnn_amd.modules.functional import loss as criteria
     labels, run = [], seam._run
 
     def logged(f, label, ref, *args):
         labels.append(label)
         return run(f, label, ref, *args)
-    seam._run = logged
+    looked_up = criteria._native()                                       # (the criteria keep the seam they looked up once)
+    seam._run, criteria._NATIVE = logged, (looked_up[0], logged, looked_up[2])
     try:
         fn()
         torch.cuda.synchronize()
     finally:
-        seam._run = run
+        seam._run, criteria._NATIVE = run, looked_up
     return labels
 
 
@@ -147,15 +156,110 @@ def replayed_step(args, dev):
     return out
 
 
+def _dml_arm(dev):
+    """(once, graph, launch counts) of this process's arm: PVCNN_FUSED_DML=0 in the environment makes it the composed one."""
+    import pvcnn_amd.modules as M
+    from pvcnn_amd.modules.functional import loss as L
+    b, c, s = SHAPES[0]
+    g = torch.Generator().manual_seed(0)
+    x0 = (4.0 * torch.randn(b, c, s, generator=g)).to(dev).requires_grad_()
+    x1 = (4.0 * torch.randn(b, c, s, generator=g)).to(dev).requires_grad_()
+    y = torch.randint(0, c, (b, s), generator=g).to(dev)
+    if L.dml_enabled:
+        pair = M.DMLPairLoss()
+        assert PF.dml_pair_loss_is_fused(x0, x1, y)
+    else:
+        criterion, criterion_dml = M.CrossEntropyLoss(), M.KLLoss()
+        assert PF.cross_entropy_is_fused(x0, y) and not PF.kl_loss_is_fused(x0, x1)
+
+        def pair(outputs, outputs_student, targets):
+            return (criterion(outputs, targets) + criterion_dml(outputs_student, outputs),
+                    criterion(outputs_student, targets) + criterion_dml(outputs, outputs_student))
+
+    def once():
+        x0.grad = x1.grad = None
+        loss, loss_student = pair(x0, x1, y)
+        loss.backward()
+        loss_student.backward()
+        return loss, loss_student
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            once()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        losses = once()
+    between_events(once, 500)
+    between_events(graph.replay, 500)
+    kernels = device_kernels(once)
+    info = {'arm': 'fused' if L.dml_enabled else 'composed', 'device': torch.cuda.get_device_name(0),
+            'device_kernels': None if kernels is None else len(kernels),
+            'device_kernel_names': None if kernels is None else sorted(set(n[:60] for n in kernels)),
+            'native_calls': native_calls(once), 'losses': [v.item() for v in losses]}
+    return once, graph, info
+
+
+def _dml_round(once, graph, iters):
+    return {'replay': round(1e3 * between_events(graph.replay, iters), 3), 'eager': round(1e3 * between_events(once, iters), 3)}
+
+
+def dml_child(args, dev):
+    """The composed arm: set up, say so, then one round per line on stdin until it closes."""
+    once, graph, info = _dml_arm(dev)
+    print(json.dumps(info), flush=True)
+    for _ in sys.stdin:
+        print(json.dumps(_dml_round(once, graph, args.dml_iters)), flush=True)
+
+
+def dml_pair(args, dev):
+    import subprocess
+    env = dict(os.environ, PVCNN_FUSED_DML='0')
+    child = subprocess.Popen([sys.executable, os.path.abspath(__file__), '--dml-child', '--dml-iters', str(args.dml_iters)], env=env,
+                             stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+    try:
+        base = json.loads(child.stdout.readline())
+        once, graph, mine = _dml_arm(dev)
+        assert base['arm'] == 'composed' and mine['arm'] == 'fused', (base['arm'], mine['arm'])
+        rounds = {'composed': [], 'fused': []}
+        for _ in range(args.rounds):
+            child.stdin.write('round\n')
+            child.stdin.flush()
+            rounds['composed'].append(json.loads(child.stdout.readline()))
+            rounds['fused'].append(_dml_round(once, graph, args.dml_iters))
+    finally:
+        child.stdin.close()
+        child.wait(timeout=60)
+    out = {'measurement': 'DML criterion pair, forward + both backwards', 'shape': list(SHAPES[0]), 'iters_per_round': args.dml_iters,
+           'rounds': args.rounds, 'device': mine['device'], 'unit': 'us per forward + both backwards', 'composed': base, 'fused': mine}
+    for mode in ('replay', 'eager'):
+        a, b = [r[mode] for r in rounds['composed']], [r[mode] for r in rounds['fused']]
+        spread = max(a) - min(a)
+        out[mode] = {'composed': a, 'fused': b, 'composed_spread': round(spread, 3),
+                     'gain_median': round(sorted(a)[len(a) // 2] - sorted(b)[len(b) // 2], 3),
+                     'faster_in_every_round_by_more_than_the_spread': bool(min(a) - max(b) > spread)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=200, help='criterion forward + backward passes per round')
     ap.add_argument('--steps', type=int, default=20, help='replayed training steps per round')
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--skip-step', action='store_true', help='the criterion alone, without the cfg2 step')
+    ap.add_argument('--dml', action='store_true', help='the deep-mutual-learning criterion pair only: composed (child process) against fused')
+    ap.add_argument('--dml-iters', type=int, default=2000, help='DML forward + backward passes per round')
+    ap.add_argument('--dml-child', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'loss_bench needs a GPU'
     dev = torch.device('cuda:0')
+    if args.dml_child:
+        return dml_child(args, dev)
+    if args.dml:
+        print(json.dumps(dml_pair(args, dev)), flush=True)
+        return
     for shape in SHAPES:
         print(json.dumps(criterion_alone(shape, args, dev)), flush=True)
     if not args.skip_step:
