@@ -957,6 +957,59 @@ PVCNN_API int pvcnn_dml_pair_bwd(const float *a, long long a_bstride, const floa
                                  long long t_bstride, const float *weight, const float *grad_out, long long B, int C, long long S,
                                  long long ignore_index, int side, const void *workspace, float *grad, void *stream);
 
+/* ---- KITTI frames: a LiDAR sweep, a calibration and 2-D boxes -> frustums (csrc/frames.hip; an additive group: the ABI version does not
+ * move).  The reference reads prepared pickles and has no code for this stage; THIS is its definition, restated in numpy by
+ * tests/frames_truth.py.  All geometry is fp64, one rounding per operation, sums left to right; a comparison with NaN is false.
+ *
+ * calib (33) fp64: P (3, 4), V2C (3, 4), R0 (3, 3), row-major, in that order.  A scan row (x, y, z, r) is fp32, widened:
+ *   ref_i  = ((V2C[i,0] x + V2C[i,1] y) + V2C[i,2] z) + V2C[i,3]
+ *   rect_i = (R0[i,0] ref_0 + R0[i,1] ref_1) + R0[i,2] ref_2
+ *   img_i  = ((P[i,0] rect_0 + P[i,1] rect_1) + P[i,2] rect_2) + P[i,3]
+ *   u = img_0 / img_2, v = img_1 / img_2;   in_image = u >= 0 & u < width & v >= 0 & v < height & x > clip_distance
+ *   (img_2 == 0 needs no special case: an infinite or NaN u fails a comparison)
+ *   rows[i] = (fp32 rect_0, fp32 rect_1, fp32 rect_2, r);  uv[i] = (u, v).  The scan has n points (count[0] when `count` is not NULL,
+ *   clamped to [0, cap]); rows, uv and in_image beyond them are zero.
+ * boxes (M, PVCNN_FRAME_BOX_COLUMNS) fp64, one row per 2-D box, every angle-dependent scalar computed on the host:
+ *   [0..3] xmin ymin xmax ymax   [4] 1 when a 3-D box follows, else 0   [5..7] h w l   [8..10] tx ty tz   [11, 12] cos ry, sin ry
+ *   [13, 14] cos, sin of rotation_angle = pi / 2 + frustum_angle   [15] rotation_angle   [16] class id   [17] score
+ *   point in box m:  in_image & u >= xmin & u < xmax & v >= ymin & v < ymax
+ *   label (3-D box given), on the STORED fp32 coordinates widened: d = rect - t, xl = c dx - s dz, zl = s dx + c dz,
+ *   inside = in box m & |xl| <= l / 2 & |zl| <= w / 2 & dy <= 0 & dy >= -h.
+ * A point tile is PVCNN_FRAME_TILE consecutive points; tiles = pvcnn_frame_tiles(cap) (0 for a cap outside [1, 2^30]).
+ *   mask / label_mask (M, tiles) 64-bit words: bit j of word [m][t] says point 64 t + j lies in box m / in its 3-D box;
+ *   prefix (M, tiles + 1) int32: exclusive prefix of the tile counts, [m][tiles] the total;  counts (M, 2) int32: (selected, positives).
+ *   label_mask may be NULL (no 3-D boxes: positives are 0).
+ * pvcnn_frame_pack: rows (and labels, uint8, may be NULL) of box kept[w] to out_rows[offsets[w] + k], k-th selected point in ascending
+ *   point index, for w < W; offsets (W + 1) int64 from the caller (offsets[w + 1] - offsets[w] = the box's count), R = all rows of
+ *   out_rows: nothing is written beyond an item's own range or R.
+ * pvcnn_frame_batch: for m < M with k = counts[m][0] selected points, position p of num_points takes choices[m][p] clamped to [0, k)
+ *   (parity mode) or mulhi(Philox4x32-10(counter (p, m, lo32 seed[1], 0), key seed[0]).x, k), as pvcnn_batch_* draw; the point at that
+ *   position (ascending point index) is found through the tile prefix; with `rotate`, x' = fp32(x c + z (-s)), z' = fp32(x s + z c) in
+ *   fp64 from the fp32 row (c, s = columns 13, 14).  features (Bmax, 4, num_points), one_hot_vectors (Bmax, K), rotation_angle (Bmax)
+ *   fp32, rgb_score (Bmax) fp64, valid (Bmax) bytes.  A box with k < max(min_points, 1) or ymax - ymin < min_box_height, and every row
+ *   m >= M, is all zero with valid = 0.
+ * pvcnn_frame_rotate_rows: the same rotation of packed rows (R, 4) in place, item w (rows offsets[w] .. offsets[w + 1]) by
+ *   cos_sin[w] = (cos, sin) fp64.
+ * No entry point allocates, synchronises or uses an atomic: the same bits for the same inputs.  scan, rows, uv, out_rows: 16-byte
+ * aligned. */
+#define PVCNN_FRAME_TILE 64
+#define PVCNN_FRAME_BOX_COLUMNS 18
+#define PVCNN_FRAME_MAX_BOXES 4096
+PVCNN_API long long pvcnn_frame_tiles(long long cap);
+PVCNN_API int pvcnn_frame_project(const float *scan, long long cap, long long n, const int *count, const double *calib, double width,
+                                  double height, double clip_distance, float *rows, double *uv, unsigned char *in_image, void *stream);
+PVCNN_API int pvcnn_frame_count(const double *uv, const unsigned char *in_image, const float *rows, long long cap, const double *boxes,
+                                int M, unsigned long long *mask, unsigned long long *label_mask, int *prefix, int *counts, void *stream);
+PVCNN_API int pvcnn_frame_pack(const float *rows, long long cap, const unsigned long long *mask, const unsigned long long *label_mask,
+                               const int *prefix, int M, const long long *kept, const long long *offsets, long long W, long long R,
+                               float *out_rows, unsigned char *out_labels, void *stream);
+PVCNN_API int pvcnn_frame_batch(const float *rows, long long cap, const unsigned long long *mask, const int *prefix, const int *counts,
+                                const double *boxes, int M, int Bmax, int num_points, int K, int rotate, int min_points,
+                                double min_box_height, const int *choices, const long long *seed, float *features,
+                                float *one_hot_vectors, float *rotation_angle, double *rgb_score, unsigned char *valid, void *stream);
+PVCNN_API int pvcnn_frame_rotate_rows(float *rows, long long R, const long long *offsets, long long W, const double *cos_sin,
+                                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,13 @@ SIGNATURES = {
     'pvcnn_dml_pair_partials': (_i, [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _ll, _ll, _vp, _vp]),
     'pvcnn_dml_pair_finalize': (_i, [_ll, _i, _ll, _vp, _vp, _vp, _vp]),
     'pvcnn_dml_pair_bwd': (_i, [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _ll, _i, _ll, _ll, _i, _vp, _vp, _vp]),
+    # KITTI frames (csrc/frames.hip): scan + calibration + 2-D boxes -> frustums
+    'pvcnn_frame_tiles': (_ll, [_ll]),
+    'pvcnn_frame_project': (_i, [_vp, _ll, _ll, _vp, _vp, _d, _d, _d, _vp, _vp, _vp, _vp]),
+    'pvcnn_frame_count': (_i, [_vp, _vp, _vp, _ll, _vp, _i] + [_vp] * 5),
+    'pvcnn_frame_pack': (_i, [_vp, _ll, _vp, _vp, _vp, _i, _vp, _vp, _ll, _ll, _vp, _vp, _vp]),
+    'pvcnn_frame_batch': (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d] + [_vp] * 8),
+    'pvcnn_frame_rotate_rows': (_i, [_vp, _ll, _vp, _ll, _vp, _vp]),
 }
 
 _lib = None

@@ -410,13 +410,11 @@ class DeviceFrustumKitti(_Store):
             if class_name_to_size_template_id is None or size_templates is None:
                 raise ValueError('class_name_to_size_template_id and size_templates are required with ground truth')
         rows, labels = [], []
-        f64 = np.zeros((w, 1 if self.rgb_detection else 4), dtype=np.float64)
-        f32 = np.zeros((w, k + (1 if self.rgb_detection else 5)), dtype=np.float32)
-        i64 = np.zeros((w, 4), dtype=np.int64)
+        tables = self._new_item_tables(w)
         for i in range(w):
-            rotation_angle = np.pi / 2.0 + frustum_rotation_angles[i]
-            name = class_names[i]
-            f32[i, class_id[name]] = 1
+            rotation_angle = self._fill_item(tables, i, class_names[i], frustum_rotation_angles[i], class_id,
+                                             None if self.rgb_detection else (boxes_3d[i], heading_angles[i], sizes[i]),
+                                             _rgb_probs[i] if self.rgb_detection else None, class_name_to_size_template_id, size_templates)
             cloud = np.asarray(point_clouds[i])
             if cloud.ndim != 2 or cloud.shape[1] != 4:
                 raise ValueError(f'point clouds of shape (n, 4) expected, got {cloud.shape}')
@@ -424,27 +422,107 @@ class DeviceFrustumKitti(_Store):
             if self.frustum_rotate:
                 cloud = rotate_points_along_y(np.copy(cloud), rotation_angle)
             rows.append(cloud)
-            if self.rgb_detection:
-                f32[i, k] = np.asarray(rotation_angle).astype(np.float32)
-                f64[i, 0] = _rgb_probs[i]
-                continue
-            labels.append(np.asarray(mask_logits[i]).astype(np.int64))
-            center = (boxes_3d[i][0, :] + boxes_3d[i][6, :]) / 2.0
-            heading_angle = heading_angles[i]
-            if self.frustum_rotate:
-                center = rotate_points_along_y(np.expand_dims(center, 0), rotation_angle).squeeze()
-                heading_angle = heading_angle - rotation_angle
-            f64[i, :3] = center
-            f64[i, 3] = np.sqrt(np.sum(center[0] ** 2 + center[1] ** 2))
-            for fl, angle in enumerate((heading_angle, np.pi - heading_angle)):
-                i64[i, fl], residual = angle_to_bin_id(angle, self.num_heading_angle_bins)
-                f32[i, k + fl] = np.array(residual, dtype=np.float32)
-            f32[i, k + 2:k + 5] = (np.asarray(sizes[i]) - np.asarray(size_templates[name])).astype(np.float32)
-            i64[i, 2], i64[i, 3] = class_name_to_size_template_id[name], class_id[name]
+            if not self.rgb_detection:
+                labels.append(np.asarray(mask_logits[i]).astype(np.int64))
         self._pack(rows, None if self.rgb_detection else labels, device)
+        self._upload_item_tables(tables)
+
+    def _new_item_tables(self, w):
+        k = self.num_classes
+        return (np.zeros((w, 1 if self.rgb_detection else 4), dtype=np.float64),
+                np.zeros((w, k + (1 if self.rgb_detection else 5)), dtype=np.float32), np.zeros((w, 4), dtype=np.int64))
+
+    def _fill_item(self, tables, i, name, frustum_rotation_angle, class_id, truth, prob, class_name_to_size_template_id, size_templates):
+        """Row i of the per-item tables: everything about an item that no draw decides, in the reference's arithmetic.  truth:
+        (corners (8, 3), heading angle, size) or None (the detection form, with `prob`).  -> the item's rotation angle."""
+        f64, f32, i64 = tables
+        k = self.num_classes
+        rotation_angle = np.pi / 2.0 + frustum_rotation_angle
+        f32[i, class_id[name]] = 1
+        if truth is None:
+            f32[i, k] = np.asarray(rotation_angle).astype(np.float32)
+            f64[i, 0] = prob
+            return rotation_angle
+        box_3d, heading_angle, size = truth
+        center = (box_3d[0, :] + box_3d[6, :]) / 2.0
+        if self.frustum_rotate:
+            center = rotate_points_along_y(np.expand_dims(center, 0), rotation_angle).squeeze()
+            heading_angle = heading_angle - rotation_angle
+        f64[i, :3] = center
+        f64[i, 3] = np.sqrt(np.sum(center[0] ** 2 + center[1] ** 2))
+        for fl, angle in enumerate((heading_angle, np.pi - heading_angle)):
+            i64[i, fl], residual = angle_to_bin_id(angle, self.num_heading_angle_bins)
+            f32[i, k + fl] = np.array(residual, dtype=np.float32)
+        f32[i, k + 2:k + 5] = (np.asarray(size) - np.asarray(size_templates[name])).astype(np.float32)
+        i64[i, 2], i64[i, 3] = class_name_to_size_template_id[name], class_id[name]
+        return rotation_angle
+
+    def _upload_item_tables(self, tables):
+        f64, f32, i64 = tables
         self.item_f64, self.item_f32 = torch.from_numpy(f64).to(self.device), torch.from_numpy(f32).to(self.device)
         self.item_i64 = None if self.rgb_detection else torch.from_numpy(i64).to(self.device)
         self._tables = self._tables + ['item_f64', 'item_f32', 'item_i64']
+
+    @classmethod
+    def from_frustums(cls, frames, num_points, classes=('Car', 'Pedestrian', 'Cyclist'), num_heading_angle_bins=12,
+                      class_name_to_size_template_id=None, size_templates=None, random_flip=False, random_shift=False,
+                      frustum_rotate=False):
+        """From `frames.extract_frustums` results (one `FrameFrustums` or a list, all with or all without ground truth, on one
+        device): rows, labels and offsets are concatenated on the device in list order -- the points never visit the host -- and the
+        per-item tables come from the frames' small host arrays through the constructor's own code.  With frustum_rotate the packed
+        rows are rotated by one launch (csrc/frames.hip) in the elementwise fp64 form x' = x c + z (-s), z' = x s + z c, rounded once:
+        within one fp32 ulp of the constructor's BLAS product.  Serves the ground-truth form and the rgb-detection form."""
+        from . import frames as _frames
+        frames = [frames] if hasattr(frames, 'rows') else list(frames)
+        frames = [f for f in frames if len(f)]
+        if not frames:
+            raise ValueError('an empty split cannot be stored')
+        truth = frames[0].labels is not None
+        if any((f.labels is not None) != truth for f in frames):
+            raise ValueError('frames with and without ground truth cannot share a store')
+        if int(num_points) < 1:
+            raise ValueError('num_points must be positive')
+        device = frames[0].rows.device
+        if device.type != 'cuda' or any(f.rows.device != device for f in frames):
+            raise RuntimeError('from_frustums needs the frustums of every frame on one CUDA (HIP) device -- there is no CPU implementation')
+        self = cls.__new__(cls)
+        self.rgb_detection = not truth
+        self.num_points, self.classes, self.device = int(num_points), tuple(classes), device
+        self.num_classes = len(self.classes)
+        self.num_heading_angle_bins = int(num_heading_angle_bins)
+        self.random_flip, self.random_shift = bool(random_flip), bool(random_shift)
+        self.frustum_rotate = bool(frustum_rotate)
+        class_id = {c: i for i, c in enumerate(self.classes)}
+        names = [n for f in frames for n in f.class_names]
+        if any(c not in class_id for c in names):
+            raise ValueError(f'class names must be among {self.classes}')
+        if truth and (class_name_to_size_template_id is None or size_templates is None):
+            raise ValueError('class_name_to_size_template_id and size_templates are required with ground truth')
+        w = len(names)
+        tables = self._new_item_tables(w)
+        cos_sin = np.zeros((w, 2), dtype=np.float64)
+        i = 0
+        for f in frames:
+            for j in range(len(f)):
+                rotation_angle = self._fill_item(tables, i, f.class_names[j], f.frustum_angles[j], class_id,
+                                                 (f.boxes_3d[j], f.heading_angles[j], f.sizes[j]) if truth else None,
+                                                 None if truth else f.scores[j], class_name_to_size_template_id, size_templates)
+                cos_sin[i] = np.cos(rotation_angle), np.sin(rotation_angle)
+                i += 1
+        counts = np.concatenate([np.asarray(f.counts, dtype=np.int64) for f in frames])
+        offsets = np.zeros(w + 1, dtype=np.int64)
+        np.cumsum(counts, out=offsets[1:])
+        self.max_n = int(counts.max())
+        self.offsets = torch.from_numpy(offsets).to(device)
+        self.rows = torch.cat([f.rows for f in frames]).contiguous()
+        self.labels = torch.cat([f.labels for f in frames]).contiguous() if truth else None
+        if self.rows.shape[0] != int(offsets[-1]):
+            raise ValueError('the frames\' counts do not add up to their rows')
+        if self.frustum_rotate:
+            _frames._call('frame_rotate_rows', self.rows, self.rows, self.rows.shape[0], self.offsets, w, torch.from_numpy(cos_sin).to(device))
+        self._tables = ['rows', 'labels', 'offsets']
+        self._upload_item_tables(tables)
+        return self
 
     @classmethod
     def from_rgb_detection(cls, point_clouds, class_names, frustum_rotation_angles, probs, num_points,
