@@ -10,18 +10,12 @@
 // Sums are accumulated in fp32 per workgroup slice (<= 8192 elements) and combined in fp64.
 #include <algorithm>
 
-#include "common.h"
+#include "wave.h"
 
 namespace pvcnn {
 
 constexpr int kBnThreads = 256;
 constexpr int kBnSlice = 8192;   // elements of one (b, c) row handled by one workgroup
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 // block-wide sum of two values; result valid in thread 0
 __device__ __forceinline__ void block_sum2(float &a, float &b, float *sm) {
@@ -85,8 +79,7 @@ __global__ __launch_bounds__(64) void bn_finalize_kernel(const float2 *__restric
   if (counter != nullptr && c == 0 && threadIdx.x == 0) *counter += 1;       // BatchNorm's num_batches_tracked (one launch less per layer)
   double s = 0.0, q = 0.0;
   for (int i = threadIdx.x; i < nparts; i += 64) { const float2 p = part[(size_t)c * nparts + i]; s += p.x; q += p.y; }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { s += __shfl_xor(s, d); q += __shfl_xor(q, d); }
+  wave_sum2(s, q);
   if (threadIdx.x == 0) {
     const double ms = s / count;                          // mean of (x - shift)
     const double m = ms + (shift ? (double)shift[c] : 0.0);
@@ -260,8 +253,7 @@ __global__ __launch_bounds__(kBnThreads) void bnact_bwd_reduce_kernel(const floa
       const unsigned long long w = peek64(reinterpret_cast<const unsigned long long *>(part + (size_t)c * nparts + i));
       ds += __uint_as_float((uint32_t)w); dq += __uint_as_float((uint32_t)(w >> 32));
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { ds += __shfl_xor(ds, d); dq += __shfl_xor(dq, d); }
+    wave_sum2(ds, dq);
     if (threadIdx.x == 0) { fold.dbeta[c] = (float)ds; fold.dgamma[c] = (float)dq; }
   }
 }
@@ -276,7 +268,7 @@ __global__ __launch_bounds__(64) void bnact_bwd_finalize_kernel(const float2 *__
   double s = 0.0, q = 0.0;
   for (int i = threadIdx.x; i < nparts; i += 64) { const float2 p = part[(size_t)c * nparts + i]; s += p.x; q += p.y; }
 #pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) { s += __shfl_xor(s, d); q += __shfl_xor(q, d); }
+  for (int d = 32; d >= 1; d >>= 1) { s += __shfl_xor(s, d); q += __shfl_xor(q, d); }   // wave_sum2, kept written out: the call costs this kernel a wait state
   if (threadIdx.x == 0) { dbeta[c] = (float)s; dgamma[c] = (float)q; }
 }
 
@@ -457,9 +449,7 @@ __global__ __launch_bounds__(256) void bnact_apply_pb_kernel(const float *__rest
               if (e1 > bv) { bv = e1; bi = 1; }
               if (e2 > bv) { bv = e2; bi = 2; }
               if (e3 > bv) { bv = e3; bi = 3; }
-              uint32_t wv = bv;
-#pragma unroll
-              for (int o = 32; o > 0; o >>= 1) wv = max(wv, (uint32_t)__shfl_xor((int)wv, o));
+              const uint32_t wv = wave_max(bv);
               const unsigned long long holders = __ballot(bv == wv);
               if (lane == __ffsll((long long)holders) - 1)
                 atomicMax(&row_keys[(size_t)b * C + c], ((unsigned long long)wv << 32) | (unsigned long long)(~(uint32_t)(p0 + pos + bi)));
@@ -592,8 +582,8 @@ extern "C" int pvcnn_bnact_apply_rowmax(const float *x, const float *gamma, cons
   PVCNN_REQUIRE(B > 0 && C > 0 && S > 0 && x && y && mean && rstd && y_amax && row_keys, "bad argument");
   PVCNN_REQUIRE(y_batch_stride == 0 || (y_batch_stride >= (long)C * S && y_batch_stride % 4 == 0), "y_batch_stride: 0, or >= C * S and a multiple of 4");
   PVCNN_REQUIRE(B <= 65535 && C <= 65535, "batch or channel count > 65535");
-  // (256 % amax_seg == 0: the row-maximum butterfly assumes every lane of the workgroup's 256 positions is active -- a segment length
-  //  that does not divide 256, e.g. 12 -> span 252, would leave lanes out of the __shfl_xor / __ballot: undefined winners)
+  // (256 % amax_seg == 0: the row-maximum butterfly (wave.h: wave_max) assumes every lane of the workgroup's 256 positions is active --
+  //  a segment length that does not divide 256, e.g. 12 -> span 252, would leave lanes out of the __shfl_xor / __ballot: undefined winners)
   PVCNN_REQUIRE(amax_seg_in_range(amax_seg), kAmaxSegRange);
   PVCNN_REQUIRE(amax_seg % 4 == 0 && 256 % amax_seg == 0 && S % 256 == 0,
                 "the row-maximum pass additionally needs S % 256 == 0 and amax_seg a multiple of 4 that divides 256");
@@ -777,7 +767,7 @@ struct CatSources {
 
 __global__ __launch_bounds__(256) void concat_points_kernel(CatSources src, int N, int vec, float *__restrict__ out,
                                                             uint32_t *__restrict__ amax, unsigned *__restrict__ ticket) {
-  __shared__ uint32_t wave_max[4];
+  __shared__ uint32_t s_wave_max[4];
   const int b = blockIdx.y, p0 = blockIdx.x * 256;
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, pos = p0 + 4 * lane;
   const int Ctot = src.c0[src.n];
@@ -830,11 +820,11 @@ __global__ __launch_bounds__(256) void concat_points_kernel(CatSources src, int 
   }
   if (amax != nullptr) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-    if (lane == 0) wave_max[wave] = m;
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));   // wave_max, kept written out: the call flips two branches here
+    if (lane == 0) s_wave_max[wave] = m;
     lds_barrier();
     if (tid == 0) {
-      const uint32_t t = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
+      const uint32_t t = max(max(s_wave_max[0], s_wave_max[1]), max(s_wave_max[2], s_wave_max[3]));
       uint32_t *slot = &amax[1 + (size_t)b * gridDim.x + blockIdx.x];
       if (gridDim.z > 1) {                                   // (a returning atomic when a ticket follows: it has been performed)
         if (ticket != nullptr) { const uint32_t old = atomicMax(slot, t); asm volatile("" ::"v"(old) : "memory"); }

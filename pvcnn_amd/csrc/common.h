@@ -100,83 +100,6 @@ __device__ __forceinline__ bool ticket_take(unsigned *ticket, unsigned total) {
   __syncthreads();
   return s_last_workgroup != 0;
 }
-
-// out[0] = max over the table out[1 .. T] of an amax buffer, by the calling workgroup (every thread calls; <= 1024 threads).  Used by
-// the workgroup that takes the last ticket in the kernels that PUBLISH the table (see ticket_take): the entries are peeked.
-// (single wave: the 64 lanes of the wave that took the last ticket; T small -- see the callers' bounds)
-__device__ __forceinline__ void amax_table_max_wave(uint32_t *out, long T) {
-  uint32_t m = 0;
-  for (long i = threadIdx.x & 63; i < T; i += 64) m = max(m, peek32(out + 1 + i));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-  if ((threadIdx.x & 63) == 0) out[0] = m;
-}
-__device__ __forceinline__ void amax_table_max(uint32_t *out, long T) {
-  __shared__ uint32_t s_amax_red[16];
-  uint32_t m = 0;
-  for (long i = threadIdx.x; i < T; i += blockDim.x) m = max(m, peek32(out + 1 + i));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-  if ((threadIdx.x & 63) == 0) s_amax_red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < (int)((blockDim.x + 63) >> 6); ++w) m = max(m, s_amax_red[w]);
-    out[0] = m;
-  }
-}
-
-// (ABI v12) max |x| of the tensor behind an amax buffer, for every thread of the calling workgroup (all of them call; two barriers):
-// T > 0: the maximum of the table buf[1 .. T] -- word [0] is not read, its producer may have left it unwritten (PVCNN_TABLE_ONLY:
-// no one-workgroup launch behind the table pass); T == 0: buf[0] (a 1-word buffer, or an amax buffer with its word [0]).
-__device__ __forceinline__ uint32_t amax_table_value(const uint32_t *__restrict__ buf, long T) {
-  if (T <= 0) return buf[0];
-  __shared__ uint32_t s_amax_val[17];
-  uint32_t m = 0;
-  for (long i = threadIdx.x; i < T; i += blockDim.x) m = max(m, buf[1 + i]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-  if ((threadIdx.x & 63) == 0) s_amax_val[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < (int)((blockDim.x + 63) >> 6); ++w) m = max(m, s_amax_val[w]);
-    s_amax_val[16] = m;
-  }
-  __syncthreads();
-  return s_amax_val[16];
-}
-
-// Sum each of 16 per-lane values over the 32 lanes of a half-wave (lanes that differ in bits 0..4) with a
-// transposing butterfly: every step halves the number of values a lane carries (the lane keeps one half and
-// ships the other), so it takes 8+4+2+1+1 = 16 shuffles instead of 16*5.  Returns, in lane j, the total of
-// value index (j >> 1) & 15 (both lanes of a pair hold the same total).
-__device__ __forceinline__ float half_wave_sum16(const float (&v)[16], int lane) {
-  float a[8], b[4], c[2];
-  const bool b4 = lane & 16, b3 = lane & 8, b2 = lane & 4, b1 = lane & 2;
-#pragma unroll
-  for (int r = 0; r < 8; ++r) a[r] = (b4 ? v[r + 8] : v[r]) + __shfl_xor(b4 ? v[r] : v[r + 8], 16);
-#pragma unroll
-  for (int r = 0; r < 4; ++r) b[r] = (b3 ? a[r + 4] : a[r]) + __shfl_xor(b3 ? a[r] : a[r + 4], 8);
-#pragma unroll
-  for (int r = 0; r < 2; ++r) c[r] = (b2 ? b[r + 2] : b[r]) + __shfl_xor(b2 ? b[r] : b[r + 2], 4);
-  float d = (b1 ? c[1] : c[0]) + __shfl_xor(b1 ? c[0] : c[1], 2);
-  d += __shfl_xor(d, 1);
-  return d;
-}
-// The same for 8 values per lane (7 + 2 shuffles): returns, in lane j, the total of value index (j >> 2) & 7.  Every total is the
-// butterfly over the lane bits 4, 3, 2, 1, 0 in that order, like half_wave_sum16's: value q of an 8-value call carries the same
-// bits as value q of a 16-value call on the same numbers (fp32 addition commutes; the tree is the same).
-__device__ __forceinline__ float half_wave_sum8(const float (&v)[8], int lane) {
-  float a[4], b[2];
-  const bool b4 = lane & 16, b3 = lane & 8, b2 = lane & 4;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) a[r] = (b4 ? v[r + 4] : v[r]) + __shfl_xor(b4 ? v[r] : v[r + 4], 16);
-#pragma unroll
-  for (int r = 0; r < 2; ++r) b[r] = (b3 ? a[r + 2] : a[r]) + __shfl_xor(b3 ? a[r] : a[r + 2], 8);
-  float c = (b2 ? b[1] : b[0]) + __shfl_xor(b2 ? b[0] : b[1], 4);
-  c += __shfl_xor(c, 2);
-  c += __shfl_xor(c, 1);
-  return c;
-}
 #endif
 
 }  // namespace pvcnn

@@ -58,8 +58,7 @@ __global__ __launch_bounds__(512) void absmax_kernel(const float *__restrict__ x
   }
   for (; i < n4; i += stride) take(x4[i]);
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) m = max(m, __float_as_uint(fabsf(x[(n4 << 2) + threadIdx.x])));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+  m = wave_max(m);
   __shared__ uint32_t red[8];
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
@@ -147,15 +146,8 @@ __global__ __launch_bounds__(1024) void absmax_tiles_reduce_kernel(uint32_t *__r
   __shared__ uint32_t red[16];
   uint32_t m = 0;
   for (long i = threadIdx.x; i < T; i += 1024) m = max(m, out[1 + i]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 1; w < 16; ++w) m = max(m, red[w]);
-    out[0] = m;
-  }
+  m = wg_max<16>(m, red);
+  if (threadIdx.x == 0) out[0] = m;
 }
 
 // f16x2 weights: one workgroup per (padded) output channel finds the row maximum, then writes the row's hi / lo planes in the
@@ -170,8 +162,7 @@ __device__ __forceinline__ void conv3d_weight_split_f16_row(const float *__restr
   uint32_t m = 0;
   if (co < CoE)
     for (int i = tid; i < CiE * 27; i += 256) m = max(m, __float_as_uint(fabsf(load(i / 27, i % 27))));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
+  m = wave_max(m);
   if ((tid & 63) == 0) red[tid >> 6] = m;
   __syncthreads();
   const int shift = scale_shift(max(max(red[0], red[1]), max(red[2], red[3])));
@@ -1141,7 +1132,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_f16_wide_kernel(const flo
           for (int nb = 0; nb < NBW; ++nb)
 #pragma unroll
             for (int vr = 0; vr < RPB; ++vr) {
-              const uint32_t m = wave_max_u32((RPB == 1 || vrow_e == vr) ? am[nb] : 0u);
+              const uint32_t m = wave_max((RPB == 1 || vrow_e == vr) ? am[nb] : 0u);
               if ((tid_e & 63) == 0 && m != 0u) atomicMax(aa.amax + 1 + ((size_t)cur.b * R + cur.x0 + wave) * R + cur.y0 + RPB * nb + vr, m);
             }
         }

@@ -23,7 +23,7 @@
 #include <algorithm>
 #include <stdlib.h>
 
-#include "common.h"
+#include "wave.h"
 #include "split16.h"
 
 namespace pvcnn {
@@ -667,8 +667,7 @@ __global__ __launch_bounds__(1024) void conv3d_wgrad_f16_reduce_kernel(const flo
     const int lane = tid - 896;
     float s = 0.0f;
     for (int q = lane; q < P; q += 64) s += gb_part[(size_t)q * CoP + co];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);    // fixed butterfly: deterministic
+    s = wave_sum(s);                                           // fixed butterfly: deterministic
     if (lane == 0) gb[co] = s;
   }
   __syncthreads();

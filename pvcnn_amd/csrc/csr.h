@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "slab.h"
+#include "wave.h"
 
 namespace pvcnn {
 
@@ -275,12 +276,7 @@ __device__ __forceinline__ void csr_prep_body(const EP &ep, int E, int L, const 
     int c[4], run = 0;
 #pragma unroll
     for (int u = 0; u < 4; ++u) { c[u] = coarse[tid * 4 + u]; run += c[u]; }
-    int incl = run;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const int up = __shfl_up(incl, d);
-      if (tid >= d) incl += up;
-    }
+    const int incl = wave_inclusive_scan(run, tid);
     int ex = incl - run;                          // entries before bucket 4*tid
     const int prev_last = __shfl_up(ex + run - c[3], 1);   // entries before bucket 4*tid - 1
     const int emax = max(E - 1, 0);
@@ -296,12 +292,7 @@ __device__ __forceinline__ void csr_prep_body(const EP &ep, int E, int L, const 
       ex += c[u];
     }
     if (tid == kWave - 1) cpre[kCsrCoarse] = ex;
-    int fincl = nflag;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const int up = __shfl_up(fincl, d);
-      if (tid >= d) fincl += up;
-    }
+    const int fincl = wave_inclusive_scan(nflag, tid);
     int rid = fincl - nflag - 1;                  // range id of the bucket before 4*tid
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -353,12 +344,7 @@ __device__ __forceinline__ void csr_prep_body(const EP &ep, int E, int L, const 
   int local = 0;
   for (int k = 0; k < per; ++k)
     if (t0 + k < nb) local += hist[pad32(t0 + k)];
-  int incl = local;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    const int up = __shfl_up(incl, d);
-    if ((tid & (kWave - 1)) >= d) incl += up;
-  }
+  const int incl = wave_inclusive_scan(local, tid & (kWave - 1));
   __syncthreads();   // cnt_out reads of hist are done before bins are rewritten
   if ((tid & 63) == 63) wave_tot[tid >> 6] = incl;
   __syncthreads();
@@ -556,12 +542,7 @@ static __device__ __forceinline__ void csr_order_body(const int32_t *__restrict_
   int v = 0, incl = 0;
   if (tid < 256) {                                        // exclusive prefix over the 256 buckets (waves 0..3)
     v = hist[tid];
-    incl = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const int up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
+    incl = wave_inclusive_scan(v, lane);
     if (lane == 63) wtot[tid >> 6] = incl;
   }
   __syncthreads();
@@ -596,12 +577,7 @@ static __device__ __forceinline__ void csr_order_body(const int32_t *__restrict_
   __syncthreads();
   if (tid < kGroups) {                                    // exclusive prefix over the 64 groups (wave 0)
     const int sz = gsz[tid];
-    int inc = sz;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const int up = __shfl_up(inc, d);
-      if (lane >= d) inc += up;
-    }
+    const int inc = wave_inclusive_scan(sz, lane);
     const long base = entw_range_base(st[0], r) + (inc - sz);
     const int ofs = sz > 0 ? (int)base : -1;
     gsz[tid] = ofs;

@@ -17,19 +17,13 @@
 // fp32 throughout, every sum in a fixed order (deterministic); parity: <= 1e-6 of torch's modules (tests/test_gpu_dense.py).
 #include <algorithm>
 
-#include "common.h"
+#include "wave.h"
 
 namespace pvcnn {
 
 constexpr int kDenseThreads = 256;
 constexpr int kDenseRowsMax = 64;
 constexpr size_t kDenseLdsMax = 144 * 1024;
-
-__device__ __forceinline__ float dense_wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 // x (n floats) -> LDS with 16-byte loads, four in flight per thread (the staging IS most of these launches: 64 KiB per workgroup)
 __device__ __forceinline__ void dense_stage(float *__restrict__ lds, const float *__restrict__ x, int n) {
@@ -88,15 +82,15 @@ __global__ __launch_bounds__(kDenseThreads) void dense_bn_relu_fwd_kernel(const 
   float mine = 0.0f;
 #pragma unroll
   for (int r = 0; r < RT; ++r) {
-    const float t = dense_wave_sum(acc[r]);
+    const float t = wave_sum(acc[r]);
     if (lane == r) mine = t;
   }
   const bool live = lane < rows;
   const float zv = live ? mine + (bias ? bias[co] : 0.0f) : 0.0f;
   const float inv = 1.0f / (float)rows;
-  const float m = dense_wave_sum(zv) * inv;
+  const float m = wave_sum(zv) * inv;
   const float d = live ? zv - m : 0.0f;
-  const float var = dense_wave_sum(d * d) * inv;            // biased, two-pass
+  const float var = wave_sum(d * d) * inv;            // biased, two-pass
   const float rs = 1.0f / sqrtf(var + eps);
   if (live) {
     const float pre = (gamma ? gamma[co] : 1.0f) * (d * rs) + (beta ? beta[co] : 0.0f);
@@ -133,10 +127,10 @@ __global__ __launch_bounds__(kDenseThreads) void dense_bn_relu_bwd_kernel(const 
   const float m = mean[co], rs = rstd[co], gm = gamma ? gamma[co] : 1.0f, bt = beta ? beta[co] : 0.0f;
   const float xhat = live ? (z[(size_t)lane * Cout + co] - m) * rs : 0.0f;
   const float g = (live && gm * xhat + bt > 0.0f) ? gy[(size_t)lane * Cout + co] : 0.0f;     // ReLU'(pre) * grad_y
-  const float dbeta = dense_wave_sum(g), dgamma = dense_wave_sum(g * xhat);
+  const float dbeta = wave_sum(g), dgamma = wave_sum(g * xhat);
   const float inv = 1.0f / (float)rows;
   const float gzv = live ? gm * rs * (g - dbeta * inv - xhat * (dgamma * inv)) : 0.0f;
-  const float gb = dense_wave_sum(gzv);
+  const float gb = wave_sum(gzv);
   if (live) gz[(size_t)lane * Cout + co] = gzv;
   if (lane == 0) {
     if (gbias) gbias[co] = gb;

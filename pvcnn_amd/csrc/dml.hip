@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kXentThreads) void dml_partials_kernel(const float 
       acc[0] += (double)kl_pq;
     }
   }
-  xent_block_sums(acc);
+  wg_sum(acc);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < K; ++k) parts[(size_t)k * gridDim.x + blockIdx.x] = acc[k];
@@ -107,7 +107,7 @@ __global__ __launch_bounds__(kXentThreads) void dml_finalize_kernel(const double
 #pragma unroll
     for (int k = 0; k < K; ++k) acc[k] += parts[(size_t)k * nparts + i];
   }
-  xent_block_sums(acc);
+  wg_sum(acc);
   if (threadIdx.x == 0) {
     if constexpr (kPair) {
       const double den = acc[2];                               // every point ignored: 0 / 0 = NaN, as torch

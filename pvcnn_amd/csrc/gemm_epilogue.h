@@ -2,7 +2,7 @@
 // conv3d_igemm_f16_pipe_kernel, pw_gemm_bf16_kernel, pw_gemm_f16_pipe_kernel).  pw_gemm_kernel (pointwise.hip) and the two persistent
 // wide kernels keep texts of their own and follow the same contract.
 #pragma once
-#include "common.h"
+#include "wave.h"
 #include "split16.h"
 #include <type_traits>
 
@@ -54,11 +54,6 @@ template <bool ACT> struct ActArgs {};
 template <> struct ActArgs<true> { float slope; uint32_t *amax; };
 __device__ __forceinline__ float act_tail(float v, float slope) { return v > 0.0f ? v : v * slope; }
 __device__ __forceinline__ uint32_t act_abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t m) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o));
-  return m;
-}
 // segment l of a Conv3d tile = its z row (xt, yt) = (l / TY, l % TY)  ->  row (b, x0 + xt, y0 + yt) of the (B, R, R) table
 template <int TY>
 struct ZRowIndex {

@@ -14,7 +14,7 @@
 // Nothing here uses an atomic, and every sum is taken in an order fixed by the sizes alone: two runs give the same bits.
 #include <climits>
 
-#include "common.h"
+#include "wave.h"
 
 namespace pvcnn {
 
@@ -146,16 +146,6 @@ __device__ __forceinline__ void wave_best(double &v, int &j) {
       j = oj;
     }
   }
-}
-__device__ __forceinline__ int wave_min(int j) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) j = min(j, __shfl_xor(j, o));
-  return j;
-}
-__device__ __forceinline__ int wave_sum(int n) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
-  return n;
 }
 
 struct ApData {
@@ -339,7 +329,7 @@ __global__ __launch_bounds__(kApThreads) void stats_kernel(ApData a, long long c
           }
         }
       }
-      fp += wave_sum(__popc(left));
+      fp += wave_sum((int)__popc(left));
     }
   }
   if (lane == 0) {
@@ -361,11 +351,7 @@ __global__ __launch_bounds__(kWave) void reduce_kernel(const double *__restrict_
 #pragma unroll
     for (int q = 0; q < 4; ++q) s[q] += in[c * 4 + q];
   }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s[q] += __shfl_xor(s[q], o);
-  }
+  s[0] = wave_sum(s[0]); s[1] = wave_sum(s[1]); s[2] = wave_sum(s[2]); s[3] = wave_sum(s[3]);
   if (lane == 0) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) pr[(long long)blockIdx.x * 4 + q] = s[q];

@@ -32,7 +32,7 @@
 //     skip flag set, write nothing and leave the step counter alone.
 #include <algorithm>
 
-#include "common.h"
+#include "wave.h"
 
 namespace pvcnn {
 
@@ -160,15 +160,6 @@ __global__ __launch_bounds__(256) void adam_grouped_kernel(float *__restrict__ p
   }
 }
 
-// sum over the 256 lanes of a workgroup, in a fixed order (xor butterfly per wave, then the four waves in turn); valid in thread 0
-__device__ __forceinline__ double block_sum_256(double s) {
-  __shared__ double s_wave[4];
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = s;
-  __syncthreads();
-  return ((s_wave[0] + s_wave[1]) + s_wave[2]) + s_wave[3];
-}
-
 // partials[blockIdx.x] = the sum of g[i]^2 over this workgroup's share (float4 index = workgroup * 256 + lane, stride grid * 256;
 // the n & 3 tail elements go to lanes 0..2 of workgroup 0).  Every lane adds its squares in index order in four fp32 sums.
 __global__ __launch_bounds__(256) void grad_sqsum_kernel(const float *__restrict__ g, size_t n, float *__restrict__ partials) {
@@ -182,14 +173,14 @@ __global__ __launch_bounds__(256) void grad_sqsum_kernel(const float *__restrict
     const float t = g[(n4 << 2) + threadIdx.x];
     a0 += t * t;
   }
-  const double total = block_sum_256(((double)a0 + (double)a1) + ((double)a2 + (double)a3));
+  const double total = wg_sum(((double)a0 + (double)a1) + ((double)a2 + (double)a3));
   if (threadIdx.x == 0) partials[blockIdx.x] = (float)total;
 }
 
 __global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const float *__restrict__ partials, int nparts, float *status) {
   double s = 0.0;
   for (int i = threadIdx.x; i < nparts; i += 256) s += (double)partials[i];
-  const double total = block_sum_256(s);
+  const double total = wg_sum(s);
   if (threadIdx.x == 0) {
     const float norm = (float)sqrt(total);
     const bool skip = !isfinite(total) && status[kStSkipEnabled] != 0.0f;

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(const float *__restrict__ 
   }
   if constexpr (ACT) {
     if (aa.amax != nullptr) {
-      am = wave_max_u32(am);
+      am = wave_max(am);
       if (lane == 0 && am != 0u) atomicMax(aa.amax + 1 + tile, am);
     }
   }

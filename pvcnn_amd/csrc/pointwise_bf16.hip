@@ -87,8 +87,7 @@ __device__ __forceinline__ void pw_weight_split_f16_row(const float *__restrict_
   uint32_t mx = 0;
   if (m < ME)
     for (int k = tid; k < KE; k += 256) mx = max(mx, __float_as_uint(fabsf(load(k))));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+  mx = wave_max(mx);
   if ((tid & 63) == 0) red[tid >> 6] = mx;
   __syncthreads();
   const int shift = scale_shift(max(max(red[0], red[1]), max(red[2], red[3])));

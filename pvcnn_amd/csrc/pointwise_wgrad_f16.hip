@@ -17,7 +17,7 @@
 // vmcnt(0) at every conversion: 1.09 ms).
 #include <algorithm>
 
-#include "common.h"
+#include "wave.h"
 #include "split16.h"
 
 namespace pvcnn {

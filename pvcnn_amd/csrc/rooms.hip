@@ -14,7 +14,7 @@
 // extent[3 + a] - extent[a] (max_room_*), because the subtraction is monotone.
 #include <algorithm>
 
-#include "common.h"
+#include "wave.h"
 #include "philox.h"
 
 namespace pvcnn {
@@ -45,12 +45,7 @@ inline long long scan_parts(long long n) { return (n + kRoomScanTile - 1) / kRoo
 __device__ __forceinline__ long long wg_exscan(long long v, long long &total) {
   __shared__ long long s_wave[kRoomThreads / kWave];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  long long x = v;
-#pragma unroll
-  for (int o = 1; o < kWave; o <<= 1) {
-    const long long t = __shfl_up(x, o);
-    if (lane >= o) x += t;
-  }
+  const long long x = wave_inclusive_scan(v, lane);
   __syncthreads();                                         // the previous call's readers are done
   if (lane == kWave - 1) s_wave[w] = x;
   __syncthreads();

@@ -10,17 +10,11 @@
 // over the clouds -- weight gradients and the two BatchNorm sums -- in cloud order: deterministic).  The inputs are the reduction
 // pass's partial sums as it writes them, `part` (C, B, slices, 2) (pvcnn_bnact_partial_sums): the sum over the slices happens here,
 // in slice order (as torch ops: a sum + two transposing copies per pass, 78 more launches per PVCNN++ step).
-#include "common.h"
+#include "wave.h"
 
 namespace pvcnn {
 
 constexpr int kSeMaxC = 2048, kSeMaxH = 256;
-
-__device__ __forceinline__ float se_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // (first, second) sums of channel c, cloud b over the slices of the reduction pass
 __device__ __forceinline__ float2 se_slice_sum(const float2 *__restrict__ part, int B, int slices, int b, int c) {
@@ -52,7 +46,7 @@ __global__ __launch_bounds__(256) void se_excite_fwd_kernel(const float2 *__rest
   for (int h = wave; h < H; h += 4) {
     float s = 0.0f;
     for (int c = lane; c < C; c += 64) s = fmaf(sq[c], w1[(size_t)h * C + c], s);
-    s = se_wave_sum(s);
+    s = wave_sum(s);
     s = s > 0.0f ? s : 0.0f;
     if (lane == 0) { hd[h] = s; hidden[(size_t)b * H + h] = s; }
   }
@@ -88,7 +82,7 @@ __global__ __launch_bounds__(256) void se_excite_bwd_chain_kernel(const float2 *
   for (int h = wave; h < H; h += 4) {
     float s = 0.0f;
     for (int c = lane; c < C; c += 64) s = fmaf(gp2[c], w2[(size_t)c * H + h], s);
-    s = se_wave_sum(s);
+    s = wave_sum(s);
     s = hidden[(size_t)b * H + h] > 0.0f ? s : 0.0f;
     if (lane == 0) { gp1[h] = s; g_pre1[(size_t)b * H + h] = s; }
   }

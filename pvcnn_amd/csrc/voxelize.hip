@@ -65,12 +65,9 @@ __global__ __launch_bounds__(1024) void voxel_coords_kernel(const float *__restr
   const float *c = coords + (size_t)b * 3 * N;
   double s[3] = {0.0, 0.0, 0.0};
   for (int i = tid; i < N; i += 1024) { s[0] += c[i]; s[1] += c[i + N]; s[2] += c[i + 2 * N]; }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s[a] += __shfl_xor(s[a], d);
-    if (lane == 0) red[a][wave] = s[a];
-  }
+  s[0] = wave_sum(s[0]); if (lane == 0) red[0][wave] = s[0];
+  s[1] = wave_sum(s[1]); if (lane == 0) red[1][wave] = s[1];
+  s[2] = wave_sum(s[2]); if (lane == 0) red[2][wave] = s[2];
   __syncthreads();
   if (tid < 3) {
     double t = 0.0;
@@ -86,8 +83,7 @@ __global__ __launch_bounds__(1024) void voxel_coords_kernel(const float *__restr
       const float x = c[i] - mx, y = c[i + N] - my, z = c[i + 2 * N] - mz;
       m2 = fmaxf(m2, (x * x + y * y) + z * z);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m2 = fmaxf(m2, __shfl_xor(m2, d));
+    m2 = wave_max(m2);
     if (lane == 0) fred[wave] = m2;
     __syncthreads();
     if (tid == 0) {

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kXentThreads) void xent_partials_kernel(const float
       }
     }
   }
-  xent_block_sums(acc);
+  wg_sum(acc);
   if (threadIdx.x == 0) {
 #pragma unroll
     for (int k = 0; k < kXentSums; ++k) parts[(size_t)k * gridDim.x + blockIdx.x] = acc[k];
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kXentThreads) void xent_finalize_kernel(const doubl
   }
   if (weight)
     for (int c = threadIdx.x; c < C; c += kXentThreads) acc[kXentSums] += (double)weight[c];
-  xent_block_sums(acc);
+  wg_sum(acc);
   if (threadIdx.x == 0) {
     const double W = weight ? acc[kXentSums] : (double)C, den = acc[2];
     const double num = (1.0 - eps) * acc[0] + eps / (double)C * (W * acc[1] - acc[4]);
