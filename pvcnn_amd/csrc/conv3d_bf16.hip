@@ -21,28 +21,29 @@
 //     tile WITH halo once, converting fp32 -> NS 16-bit planes on the way (v_cvt_pk_{bf16,f16}_f32 on channel pairs): xs[plane][halo voxel][16 ch] (32 B per voxel,
 //     the two 8-channel halves XOR-swizzled by bit 3 of the voxel index: the 16-byte operand reads of 32 consecutive
 //     voxels then hit 64 distinct banks);
-//   * weights arrive pre-split and pre-swizzled in exactly the LDS layout (conv3d_weight_split_kernel, once per forward):
-//     per (dx, dy) the 3 dz taps x NS planes x 64 co x 16 ci = NS * 6 KiB are one contiguous block -> straight 16-byte copies;
+//   * weights arrive pre-split and pre-swizzled as a weight image (weight_image.h states its format and holds its writers): per
+//     (dx, dy) one contiguous block of NS * 6 KiB -> straight 16-byte copies;
 //   * a consumer wave owns 64 voxels x 64 channels (2 x 2 MFMA tiles); per tap it reads 2 * NS weight fragments (from the
 //     pre-split image in global memory / L2) and 2 * NS input fragments (LDS) for 4 * (NS == 3 ? 6 : 1) MFMAs;
 //   * 41 / 61 KiB of LDS at NS = 2 / 3 for the 256-voxel tile -> 3 / 2 workgroups per CU: one stages while the others multiply;
 //   * epilogue as in conv3d.hip: C/D rows are 32 consecutive-z voxels of one channel = 128-byte rows of (B, C, R^3); bias;
 //     optional BatchNorm partial sums of (y - bias).
-// Backward-data is the same kernel on the flipped, channel-transposed weights (the split kernel's for_bwd_data mode).
+// Backward-data is the same kernel on the flipped, channel-transposed weights (the for_bwd_data image: ConvImage::source).
 #include <algorithm>
 #include <stdlib.h>
 #include <type_traits>
 
 #include "common.h"
-#include <string.h>
 #include "gemm_epilogue.h"
 #include "route.h"
 #include "split16.h"
+#include "weight_image.h"
 
 namespace pvcnn {
 
 constexpr int kCoTileB = 64;
 constexpr int kKc = 16;            // input channels per chunk = MFMA K
+static_assert(ConvImage::row_tile(0) == kCoTileB && kImageK == kKc, "weight_image.h writes the image these kernels read");
 
 __global__ __launch_bounds__(512) void absmax_kernel(const float *__restrict__ x, size_t n, uint32_t *__restrict__ out) {
   uint32_t m = 0;
@@ -150,102 +151,6 @@ __global__ __launch_bounds__(1024) void absmax_tiles_reduce_kernel(uint32_t *__r
   if (threadIdx.x == 0) out[0] = m;
 }
 
-// f16x2 weights: one workgroup per (padded) output channel finds the row maximum, then writes the row's hi / lo planes in the
-// image layout below and the row's shift to wexp[co].
-__device__ __forceinline__ void conv3d_weight_split_f16_row(const float *__restrict__ w, int Co, int Ci, int for_bwd_data,
-                                                            uint16_t *__restrict__ wts, int *__restrict__ wexp, int co) {
-  const int CiE = for_bwd_data ? Co : Ci, CoE = for_bwd_data ? Ci : Co;
-  const int chunks = ceil_div(CiE, 16), cotiles = ceil_div(CoE, 64);
-  const int cot = co >> 6, co_l = co & 63, tid = threadIdx.x;
-  auto load = [&](int ci, int tap) { return for_bwd_data ? w[((size_t)ci * Ci + co) * 27 + (26 - tap)] : w[((size_t)co * Ci + ci) * 27 + tap]; };
-  __shared__ uint32_t red[4];
-  uint32_t m = 0;
-  if (co < CoE)
-    for (int i = tid; i < CiE * 27; i += 256) m = max(m, __float_as_uint(fabsf(load(i / 27, i % 27))));
-  m = wave_max(m);
-  if ((tid & 63) == 0) red[tid >> 6] = m;
-  __syncthreads();
-  const int shift = scale_shift(max(max(red[0], red[1]), max(red[2], red[3])));
-  if (tid == 0) wexp[co] = shift;
-  const float scale = exp2_int(shift);
-  for (int i = tid; i < chunks * 27 * 8; i += 256) {             // item = (chunk, tap, channel pair)
-    const int cp = i & 7, tap = (i >> 3) % 27, chunk = (i >> 3) / 27;
-    const int ci = chunk * 16 + 2 * cp, dxy = tap / 3, dz = tap - dxy * 3;
-    const float a = (co < CoE && ci < CiE) ? load(ci, tap) * scale : 0.0f;
-    const float b = (co < CoE && ci + 1 < CiE) ? load(ci + 1, tap) * scale : 0.0f;
-    uint32_t p[2];
-    split_pair<2>(a, b, p);
-    const int pos = (((cp >> 2) ^ ((co_l >> 3) & 1)) * 8 + 2 * (cp & 3)) >> 1;     // word inside the 16-channel row
-    const size_t blk = (((size_t)chunk * 9 + dxy) * cotiles + cot) * (3 * 2 * 64 * 16);
-    uint32_t *img = reinterpret_cast<uint32_t *>(wts + blk);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) img[((size_t)(dz * 2 + s) * 64 + co_l) * 8 + pos] = p[s];
-  }
-}
-
-__global__ __launch_bounds__(256) void conv3d_weight_split_f16_kernel(const float *__restrict__ w, int Co, int Ci, int for_bwd_data,
-                                                                      uint16_t *__restrict__ wts, int *__restrict__ wexp) {
-  conv3d_weight_split_f16_row(w, Co, Ci, for_bwd_data, wts, wexp, blockIdx.x);
-}
-
-// forward AND backward-data image of one weight in one launch (a training step needs both; the weights do not change in between)
-__global__ __launch_bounds__(256) void conv3d_weight_split_f16_pair_kernel(const float *__restrict__ w, int Co, int Ci, int rows_fwd,
-                                                                           uint16_t *__restrict__ wts_f, int *__restrict__ wexp_f,
-                                                                           uint16_t *__restrict__ wts_b, int *__restrict__ wexp_b) {
-  if ((int)blockIdx.x < rows_fwd) conv3d_weight_split_f16_row(w, Co, Ci, 0, wts_f, wexp_f, blockIdx.x);
-  else conv3d_weight_split_f16_row(w, Co, Ci, 1, wts_b, wexp_b, blockIdx.x - rows_fwd);
-}
-
-// ... of EVERY registered weight of a model in one launch (the weights change once per optimizer step: 7 launches of this kind per PVCNN
-// step, 25 per PVCNN++ step become one).
-__global__ __launch_bounds__(256) void conv3d_weight_split_f16_batch_kernel(const SplitEntry *__restrict__ tab, int n) {
-  const SplitEntry e = split_entry_of(tab, n, blockIdx.x);
-  const int row = (int)(blockIdx.x - e.row_begin);
-  if (row < (int)e.rows_f) conv3d_weight_split_f16_row(e.w, (int)e.Co, (int)e.Ci, 0, e.wts_f, e.wexp_f, row);
-  else conv3d_weight_split_f16_row(e.w, (int)e.Co, (int)e.Ci, 1, e.wts_b, e.wexp_b, row - (int)e.rows_f);
-}
-
-// ---- weights: (Co, Ci, 27) fp32 -> [chunk][dxy][cotile][dz][plane][64 co][16 ci (halves swizzled)] bf16 ----
-// for_bwd_data: the convolution computed is grad_x = conv(grad_y, w') with Ci' = Co, Co' = Ci, w'[ci][co][tap] = w[co][ci][26 - tap]
-template <int NS>
-__device__ __forceinline__ void conv3d_weight_split_elem(const float *__restrict__ w, int Co, int Ci, int for_bwd_data,
-                                                         uint16_t *__restrict__ wts, long e) {
-  const int CiE = for_bwd_data ? Co : Ci, CoE = for_bwd_data ? Ci : Co;       // effective (reduction, output) channel counts
-  const int chunks = ceil_div(CiE, kKc), cotiles = ceil_div(CoE, kCoTileB);
-  const long total = (long)chunks * 9 * cotiles * 3 * kCoTileB * kKc;          // one thread per (.., dz, co, ci): writes NS planes
-  if (e >= total) return;
-  const int ci_l = (int)(e % kKc), co_l = (int)((e / kKc) % kCoTileB), dz = (int)((e / (kKc * kCoTileB)) % 3);
-  long rest = e / (kKc * kCoTileB * 3);
-  const int cot = (int)(rest % cotiles); rest /= cotiles;
-  const int dxy = (int)(rest % 9);
-  const int chunk = (int)(rest / 9);
-  const int ci = chunk * kKc + ci_l, co = cot * kCoTileB + co_l, tap = dxy * 3 + dz;
-  float v = 0.0f;
-  if (ci < CiE && co < CoE)
-    v = for_bwd_data ? w[((size_t)ci * Ci + co) * 27 + (26 - tap)] : w[((size_t)co * Ci + ci) * 27 + tap];
-  uint32_t p[NS];
-  split_bf16<NS>(v, p);
-  const int pos = ((ci_l >> 3) ^ ((co_l >> 3) & 1)) * 8 + (ci_l & 7);
-  const size_t blk = (((size_t)chunk * 9 + dxy) * cotiles + cot) * (3 * NS * kCoTileB * kKc);
-#pragma unroll
-  for (int s = 0; s < NS; ++s) wts[blk + ((size_t)(dz * NS + s) * kCoTileB + co_l) * kKc + pos] = (uint16_t)p[s];
-}
-
-template <int NS>
-__global__ __launch_bounds__(256) void conv3d_weight_split_kernel(const float *__restrict__ w, int Co, int Ci, int for_bwd_data,
-                                                                  uint16_t *__restrict__ wts) {
-  conv3d_weight_split_elem<NS>(w, Co, Ci, for_bwd_data, wts, (long)blockIdx.x * 256 + threadIdx.x);
-}
-
-// the plain-bf16 (torch.autocast) images of EVERY registered weight in one launch, forward and backward-data: the batched form of
-// conv3d_weight_split_kernel<1> (the Frustum-PVCNN step issued 15 of those).  An entry's rows are 256-element blocks here: rows_f of
-// the forward image first, then the backward-data image; wexp_* are unused (no per-row scale in this arithmetic).
-__global__ __launch_bounds__(256) void conv3d_weight_split_bf16_batch_kernel(const SplitEntry *__restrict__ tab, int n) {
-  const SplitEntry e = split_entry_of(tab, n, blockIdx.x);
-  const long local = (long)(blockIdx.x - e.row_begin);
-  if (local < (long)e.rows_f) conv3d_weight_split_elem<1>(e.w, (int)e.Co, (int)e.Ci, 0, e.wts_f, local * 256 + threadIdx.x);
-  else conv3d_weight_split_elem<1>(e.w, (int)e.Co, (int)e.Ci, 1, e.wts_b, (local - (long)e.rows_f) * 256 + threadIdx.x);
-}
 
 // Variants measured on (16,64,64,32^3), bf16x3 (fp32 kernel: 0.87 ms; 6x the MFMAs at 16x the rate = 0.28 ms at 2.4 GHz):
 //   this one (256 threads, 2 workgroups per CU, 27 taps unrolled, weights one tap ahead)   0.56 ms
@@ -362,7 +267,7 @@ __global__ __launch_bounds__(256, (NS == 3 || TX * TY * TZ == 512 || TZ <= 16) ?
   constexpr int VOX = TX * TY * TZ;
   constexpr int WM = VOX <= 128 ? 2 : 1, MBW = CO32 ? 1 : 2 / WM, NBW = VOX / (32 * (4 / WM));   // waves along the channels; row / column blocks per wave
   static_assert(!CO32 || WM == 1, "the 32-channel variant is for the tiles whose waves sit side by side");
-  constexpr int WBLK = 3 * NS * kCoTileB * kKc;                 // bf16 elements of one (chunk, dxy, cotile) weight block
+  constexpr int WBLK = image_block<ConvImage>(NS, kCoTileB);               // bf16 elements of one (chunk, dxy, cotile) weight block
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_u[];
   uint32_t *xs = lds_u;                                         // [NS][HS][8] words (16 bf16 per voxel)
 
@@ -418,7 +323,7 @@ __global__ __launch_bounds__(256, (NS == 3 || TX * TY * TZ == 512 || TZ <= 16) ?
 #pragma unroll
   for (int mb = 0; mb < MBW; ++mb) {
     const int row = (wm * MBW + mb) * 32 + j;
-    a_off[mb] = row * 8 + ((kh ^ ((row >> 3) & 1)) * 4);
+    a_off[mb] = row * 8 + ((kh ^ ((row >> 3) & 1)) * 4);                // (weight_image.h: row * 8 + image_half_word(row, kh), written out)
   }
   f32x16 acc[MBW][NBW];
 #pragma unroll
@@ -526,7 +431,7 @@ __global__ __launch_bounds__(256, (NS == 3 || TX * TY * TZ == 512 || TZ <= 16) ?
 #pragma unroll
       for (int mb = 0; mb < MBW; ++mb)
 #pragma unroll
-        for (int s = 0; s < NS; ++s) af[mb][s] = wq[((dz * NS + s) * kCoTileB * 8 + a_off[mb]) >> 2];
+        for (int s = 0; s < NS; ++s) af[mb][s] = wq[((dz * NS + s) * (image_slab(kCoTileB) / 2) + a_off[mb]) >> 2];
     };
     // The weight fragments of the next AD taps are in flight during this tap's MFMAs.  AD = 1 hides them behind the other waves of
     // the SIMD; small grids (R <= 16) have only one or two waves per SIMD and a tap's MFMAs take 160-320 ns, far less than an L2
@@ -613,7 +518,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const flo
                                                                        int amax_seg, ActArgs<ACT> aa, const uint32_t *__restrict__ need_rows) {
   constexpr int NS = 2, TZ = 16, HX = TX + 2, HY = TY + 2, HZ = TZ + 2, HS = HX * HY * HZ, TILE = NS * HS * 8;
   static_assert(TX * TY * TZ == 128, "4 waves, 2 x 2: 32 channels x 64 voxels each");
-  constexpr int NBW = 2, WBLK = 3 * NS * kCoTileB * kKc;
+  constexpr int NBW = 2, WBLK = image_block<ConvImage>(NS, kCoTileB);
   constexpr int ITEMS = 2 * HX * HY * (TZ / 4);                 // (channel octet, hx, hy, z quad)
   static_assert(ITEMS <= 256, "one staging item per thread");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_u[];
@@ -669,7 +574,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const flo
     for (int dz = 0; dz < 3; ++dz) bbase[nb][dz] = (uint32_t)(kh * HS + (xt * HY + yt) * HZ + zpos(zt + dz)) * 16u;
   }
   const int a_row = wm * 32 + j;
-  const uint32_t a_off = (uint32_t)(a_row * 8 + ((kh ^ ((a_row >> 3) & 1)) * 4)) * 4u;      // bytes inside one (dz, plane) slab of the image
+  const uint32_t a_off = (uint32_t)(a_row * 8 + ((kh ^ ((a_row >> 3) & 1)) * 4)) * 4u;      // bytes inside one (dz, plane) slab of the image (weight_image.h: image_half_word, written out)
   f32x16 acc[1][NBW];                                           // (one row block per wave: the shapes split_products takes)
 #pragma unroll
   for (int nb = 0; nb < NBW; ++nb)
@@ -730,9 +635,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_igemm_f16_pipe_kernel(const flo
     const char *wblk = reinterpret_cast<const char *>(wts + (((size_t)chunk * 9) * cotiles + cot) * WBLK);
     auto load_a = [&](int tap, uint4 (&af)[1][NS]) {           // uniform tap base + the lane's 32-bit offset
       const int dxy = tap / 3, dz = tap - dxy * 3;
-      const char *wq = wblk + ((size_t)dxy * cotiles * WBLK + (size_t)dz * NS * kCoTileB * kKc) * sizeof(uint16_t);
+      const char *wq = wblk + ((size_t)dxy * cotiles * WBLK + (size_t)dz * NS * image_slab(kCoTileB)) * sizeof(uint16_t);
 #pragma unroll
-      for (int s = 0; s < NS; ++s) af[0][s] = *reinterpret_cast<const uint4 *>(wq + s * (kCoTileB * kKc * 2) + a_off);
+      for (int s = 0; s < NS; ++s) af[0][s] = *reinterpret_cast<const uint4 *>(wq + s * (image_slab(kCoTileB) * 2) + a_off);
     };
     auto load_b = [&](int tap, uint4 (&bf)[NBW][NS]) {
       const int dx = tap / 9, dy = (tap / 3) % 3, dz = tap % 3;
@@ -820,7 +725,7 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_f16_wide_kernel(const flo
   static_assert(TZ == 32 || TZ == 16, "the tile spans z: R = 32 or 16");
   using G = CwGeom<TZ>;
   constexpr int NS = 2, R = TZ, TX = 4, TY = 4, HX = G::HX, HY = G::HY, HZ = G::HZ, HS = G::HS, NBW = TZ / 8, MBW = 2;
-  constexpr int HALFB = G::HALFB, TILEB = G::TILEB, WBLK = 3 * NS * kCoTileB * kKc;
+  constexpr int HALFB = G::HALFB, TILEB = G::TILEB, WBLK = image_block<ConvImage>(NS, kCoTileB);
   constexpr int RR = R * R, S = RR * R, tiles_x = R / TX, tiles_y = R / TY;
   constexpr int QZ = TZ / 4, NITEMS = 2 * HX * HY * QZ, NIT = (NITEMS + 255) / 256;       // staging items: 576 (3 per thread) / 288 (2)
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -907,14 +812,14 @@ __global__ __launch_bounds__(256, 1) void conv3d_igemm_f16_wide_kernel(const flo
   }
   // B fragment: the lane's voxel (row vrow of column block nb, z) of x plane `wave` of the tile; tap (dx, dy, dz) and nb are immediates
   const uint32_t b_off = (uint32_t)(kh * HS + (wave * HY + vrow) * HZ + vz) * 16u;
-  // A fragment: row mb * 32 + j of the 64-row slab (bytes); the swizzle bit is bit 3 of the row
+  // A fragment: row mb * 32 + j of the 64-row slab (bytes); the swizzle bit is bit 3 of the row (weight_image.h: image_half_word, written out)
   const uint32_t a_off = (uint32_t)(j * 8 + ((kh ^ ((j >> 3) & 1)) * 4)) * 4u;
   const uint32_t a_chunk = (uint32_t)(9 * cotiles) * (uint32_t)(WBLK * 2);      // bytes from a chunk's block to the next chunk's
 
   auto load_a1 = [&](uint32_t soff, int tap, int plane, int mb) {          // (tap: compile-time)
     const int dxy = tap / 3, dz = tap - dxy * 3;
     return __builtin_amdgcn_raw_buffer_load_b128(wrsrc, a_off + (uint32_t)(mb * 32 * 32),
-                                                 soff + (uint32_t)dxy * (uint32_t)(cotiles * WBLK * 2) + (uint32_t)((dz * NS + plane) * kCoTileB * kKc * 2), 0);
+                                                 soff + (uint32_t)dxy * (uint32_t)(cotiles * WBLK * 2) + (uint32_t)((dz * NS + plane) * image_slab(kCoTileB) * 2), 0);
   };
   auto load_b1 = [&](int buf, int tap, int plane, int nb) {
     const int dx = tap / 9, dy = (tap / 3) % 3, dz = tap % 3;
@@ -1212,15 +1117,27 @@ static int launch_igemm_bf16(const float *x, const uint16_t *wts, const float *b
 
 using namespace pvcnn;
 
-static size_t weight_image_bytes(int CiE, int CoE, int nsplit) {
-  return (size_t)ceil_div(CiE, kKc) * 9 * ceil_div(CoE, kCoTileB) * 3 * nsplit * kCoTileB * kKc * sizeof(uint16_t);
-}
-
-// nsplit: 1 = bf16, 3 = bf16x3, 2 = f16x2 (image followed by one int32 shift per padded output channel)
+// ---- the weight images: all of it is weight_image.h on ConvImage ----
 extern "C" size_t pvcnn_conv3d_weight_split_bytes(int Co, int Ci, int for_bwd_data, int nsplit) {
-  if (Co <= 0 || Ci <= 0 || nsplit < 1 || nsplit > 3) return 0;
-  const int CiE = for_bwd_data ? Co : Ci, CoE = for_bwd_data ? Ci : Co;
-  return weight_image_bytes(CiE, CoE, nsplit) + (nsplit == 2 ? (size_t)ceil_div(CoE, kCoTileB) * kCoTileB * sizeof(int) : 0);
+  return weight_split_bytes<ConvImage>(Co, Ci, for_bwd_data, nsplit);
+}
+extern "C" int pvcnn_conv3d_weight_split(const float *w, int Co, int Ci, int for_bwd_data, int nsplit, void *wts, void *stream) {
+  return weight_split<ConvImage>(w, Co, Ci, for_bwd_data, nsplit, wts, stream);
+}
+extern "C" int pvcnn_conv3d_weight_split_pair(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, void *stream) {
+  return weight_split_pair<ConvImage>(w, Co, Ci, wts_fwd, wts_bwd, stream);
+}
+extern "C" long pvcnn_conv3d_weight_split_pair_entry(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, long long *entry) {
+  return weight_split_pair_entry<ConvImage>(w, Co, Ci, wts_fwd, wts_bwd, entry, 2);
+}
+extern "C" int pvcnn_conv3d_weight_split_pair_batch(const void *table, int n, long total_rows, void *stream) {
+  return weight_split_pair_batch<ConvImage>(table, n, total_rows, stream, 2);
+}
+extern "C" long pvcnn_conv3d_weight_split_pair_entry_bf16(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, long long *entry) {
+  return weight_split_pair_entry<ConvImage>(w, Co, Ci, wts_fwd, wts_bwd, entry, 1);
+}
+extern "C" int pvcnn_conv3d_weight_split_pair_batch_bf16(const void *table, int n, long total_rows, void *stream) {
+  return weight_split_pair_batch<ConvImage>(table, n, total_rows, stream, 1);
 }
 
 // out[0] = max over x of the bit pattern of |x| (0 for an empty tensor); the f16x2 convolution derives its input scale from it
@@ -1272,87 +1189,6 @@ extern "C" int pvcnn_absmax_tiles(const float *x, int B, int C, long L, int seg,
   return ticket || table_only ? 0 : launch_amax_reduce(o, (long)B * nseg, s);
 }
 
-extern "C" int pvcnn_conv3d_weight_split(const float *w, int Co, int Ci, int for_bwd_data, int nsplit, void *wts, void *stream) {
-  PVCNN_REQUIRE(w && wts && Co > 0 && Ci > 0, "bad argument");
-  PVCNN_REQUIRE(nsplit >= 1 && nsplit <= 3, "nsplit must be 1 (bf16), 2 (f16x2) or 3 (bf16x3)");
-  PVCNN_REQUIRE(aligned16(wts), "wts must be 16-byte aligned");
-  const int CiE = for_bwd_data ? Co : Ci, CoE = for_bwd_data ? Ci : Co;
-  if (nsplit == 2) {
-    int *wexp = reinterpret_cast<int *>(static_cast<char *>(wts) + weight_image_bytes(CiE, CoE, 2));
-    hipLaunchKernelGGL(conv3d_weight_split_f16_kernel, dim3(ceil_div(CoE, kCoTileB) * kCoTileB), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       w, Co, Ci, for_bwd_data, static_cast<uint16_t *>(wts), wexp);
-    return check_launch("conv3d_weight_split_f16");
-  }
-  const long total = (long)ceil_div(CiE, kKc) * 9 * ceil_div(CoE, kCoTileB) * 3 * kCoTileB * kKc;
-  const dim3 grid((unsigned)((total + 255) / 256));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (nsplit == 1) hipLaunchKernelGGL(conv3d_weight_split_kernel<1>, grid, dim3(256), 0, s, w, Co, Ci, for_bwd_data, static_cast<uint16_t *>(wts));
-  else             hipLaunchKernelGGL(conv3d_weight_split_kernel<3>, grid, dim3(256), 0, s, w, Co, Ci, for_bwd_data, static_cast<uint16_t *>(wts));
-  return check_launch("conv3d_weight_split");
-}
-
-// both f16x2 images of w (forward + backward-data) in one launch; buffers sized by pvcnn_conv3d_weight_split_bytes(.., 0 / 1, 2)
-extern "C" int pvcnn_conv3d_weight_split_pair(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, void *stream) {
-  PVCNN_REQUIRE(w && wts_fwd && wts_bwd && Co > 0 && Ci > 0, "bad argument");
-  PVCNN_REQUIRE(aligned16(wts_fwd) && aligned16(wts_bwd), "images must be 16-byte aligned");
-  const int rows_f = ceil_div(Co, kCoTileB) * kCoTileB, rows_b = ceil_div(Ci, kCoTileB) * kCoTileB;
-  int *wexp_f = reinterpret_cast<int *>(static_cast<char *>(wts_fwd) + weight_image_bytes(Ci, Co, 2));
-  int *wexp_b = reinterpret_cast<int *>(static_cast<char *>(wts_bwd) + weight_image_bytes(Co, Ci, 2));
-  hipLaunchKernelGGL(conv3d_weight_split_f16_pair_kernel, dim3(rows_f + rows_b), dim3(256), 0, static_cast<hipStream_t>(stream), w, Co, Ci,
-                     rows_f, static_cast<uint16_t *>(wts_fwd), wexp_f, static_cast<uint16_t *>(wts_bwd), wexp_b);
-  return check_launch("conv3d_weight_split_pair");
-}
-
-// batched form of pvcnn_conv3d_weight_split_pair: `entry` (host, 10 int64) describes one weight and its two image buffers and returns
-// the number of workgroups it takes; the caller sets word [9] (row_begin) to the running sum and copies the table to the device.
-extern "C" long pvcnn_conv3d_weight_split_pair_entry(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, long long *entry) {
-  if (!w || !wts_fwd || !wts_bwd || !entry || Co <= 0 || Ci <= 0 || !aligned16(wts_fwd) || !aligned16(wts_bwd)) return -1;
-  const int rows_f = ceil_div(Co, kCoTileB) * kCoTileB, rows_b = ceil_div(Ci, kCoTileB) * kCoTileB;
-  SplitEntry e;
-  e.w = w;
-  e.wts_f = static_cast<uint16_t *>(wts_fwd);
-  e.wexp_f = reinterpret_cast<int *>(static_cast<char *>(wts_fwd) + weight_image_bytes(Ci, Co, 2));
-  e.wts_b = static_cast<uint16_t *>(wts_bwd);
-  e.wexp_b = reinterpret_cast<int *>(static_cast<char *>(wts_bwd) + weight_image_bytes(Co, Ci, 2));
-  e.Co = Co; e.Ci = Ci; e.rows_f = rows_f; e.tm = 0; e.row_begin = 0;
-  memcpy(entry, &e, sizeof(e));
-  return rows_f + rows_b;
-}
-
-extern "C" int pvcnn_conv3d_weight_split_pair_batch(const void *table, int n, long total_rows, void *stream) {
-  PVCNN_REQUIRE(n >= 0 && total_rows >= 0 && total_rows <= 0x7fffffffL, "bad size");
-  if (n == 0 || total_rows == 0) return 0;
-  PVCNN_REQUIRE(table && (reinterpret_cast<uintptr_t>(table) & 7) == 0, "null or misaligned table");
-  hipLaunchKernelGGL(conv3d_weight_split_f16_batch_kernel, dim3((unsigned)total_rows), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const SplitEntry *>(table), n);
-  return check_launch("conv3d_weight_split_pair_batch");
-}
-
-// ... and of the plain-bf16 images (nsplit = 1; buffers sized by pvcnn_conv3d_weight_split_bytes(.., 0 / 1, 1))
-static long conv_bf16_image_blocks(int CiE, int CoE) {
-  return ((long)ceil_div(CiE, kKc) * 9 * ceil_div(CoE, kCoTileB) * 3 * kCoTileB * kKc + 255) / 256;
-}
-
-extern "C" long pvcnn_conv3d_weight_split_pair_entry_bf16(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, long long *entry) {
-  if (!w || !wts_fwd || !wts_bwd || !entry || Co <= 0 || Ci <= 0 || !aligned16(wts_fwd) || !aligned16(wts_bwd)) return -1;
-  SplitEntry e;
-  e.w = w;
-  e.wts_f = static_cast<uint16_t *>(wts_fwd); e.wexp_f = nullptr;
-  e.wts_b = static_cast<uint16_t *>(wts_bwd); e.wexp_b = nullptr;
-  e.Co = Co; e.Ci = Ci; e.rows_f = conv_bf16_image_blocks(Ci, Co); e.tm = 0; e.row_begin = 0;
-  memcpy(entry, &e, sizeof(e));
-  return (long)e.rows_f + conv_bf16_image_blocks(Co, Ci);
-}
-
-extern "C" int pvcnn_conv3d_weight_split_pair_batch_bf16(const void *table, int n, long total_rows, void *stream) {
-  PVCNN_REQUIRE(n >= 0 && total_rows >= 0 && total_rows <= 0x7fffffffL, "bad size");
-  if (n == 0 || total_rows == 0) return 0;
-  PVCNN_REQUIRE(table && (reinterpret_cast<uintptr_t>(table) & 7) == 0, "null or misaligned table");
-  hipLaunchKernelGGL(conv3d_weight_split_bf16_batch_kernel, dim3((unsigned)total_rows), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const SplitEntry *>(table), n);
-  return check_launch("conv3d_weight_split_pair_batch_bf16");
-}
-
 extern "C" size_t pvcnn_conv3d_fwd_split_stats_parts(int B, int Co, int R, int nsplit) {
   if (B <= 0 || Co <= 0 || R <= 0) return 0;
   return route::conv3d_fwd_split_plan(B, /* Ci: no part in the slot count */ 0, Co, R, nsplit, switches()).stats_slots;
@@ -1385,13 +1221,14 @@ static int conv3d_fwd_split_impl(const float *x, const void *wts, const float *b
   const route::ConvFwdPlan p = route::conv3d_fwd_split_plan(B, Ci, Co, R, nsplit, switches());
   PVCNN_REQUIRE(!p.vec || aligned16(x), "x must be 16-byte aligned");
   const uint32_t *am = static_cast<const uint32_t *>(x_absmax);
-  const int *wexp = nsplit == 2 ? reinterpret_cast<const int *>(static_cast<const char *>(wts) + weight_image_bytes(Ci, Co, 2)) : nullptr;
+  const ImageGeom<ConvImage> image(Co, Ci, false);              // (a backward-data call names the image's own rows and depth)
+  const int *wexp = nsplit == 2 ? image.shifts(wts) : nullptr;
 #define PVCNN_IGEMM(NS, TX, TY, TZ, VEC) launch_igemm_bf16<NS, TX, TY, TZ, VEC, false, ACT>(x, w16, bias, y, B, Ci, Co, R, s, sp, am, wexp, amax_seg, aa, need)
 #define PVCNN_IGEMM_NS(TX, TY, TZ, VEC) (nsplit == 3 ? PVCNN_IGEMM(3, TX, TY, TZ, VEC) : nsplit == 2 ? PVCNN_IGEMM(2, TX, TY, TZ, VEC) : PVCNN_IGEMM(1, TX, TY, TZ, VEC))
 #define PVCNN_IGEMM_VEC(TX, TY, TZ) (p.vec ? PVCNN_IGEMM_NS(TX, TY, TZ, true) : PVCNN_IGEMM_NS(TX, TY, TZ, false))
   switch (p.kernel) {
     case route::ConvKernel::Wide: {
-      const unsigned xb = (unsigned)((size_t)B * Ci * R * R * R * 4), wb = (unsigned)weight_image_bytes(Ci, Co, 2);
+      const unsigned xb = (unsigned)((size_t)B * Ci * R * R * R * 4), wb = (unsigned)image.image_bytes(2);
 #define PVCNN_CW_LAUNCH(TZV, ABV)                                                                                                    \
       do {                                                                                                                             \
         auto kw = conv3d_igemm_f16_wide_kernel<TZV, ABV, ACT>;                                                                            \

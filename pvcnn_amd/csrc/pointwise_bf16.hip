@@ -11,7 +11,7 @@
 //   * per chunk of 16 reduction channels the 256 x 16 input tile is staged once, fp32 -> NS bf16 planes, as packed channel
 //     PAIRS with points contiguous: xs[plane][channel pair][point] (coalesced 16-byte loads in, 16-byte LDS writes, and the
 //     operand reads are conflict-free);
-//   * the weights come from a pre-split, pre-swizzled image in global memory (pw_weight_split_kernel; L2-resident), each
+//   * the weights come from a pre-split, pre-swizzled weight image in global memory (weight_image.h: PwImage; L2-resident), each
 //     lane fetching its own 16-byte A fragments, requested BEFORE the tile is staged so they land behind the staging;
 //   * C/D rows are 32 consecutive points of one channel = 128-byte rows of the channel-major (B, M, N) output; bias and the
 //     optional BatchNorm partial sums of (y - bias) ride on the epilogue.
@@ -27,104 +27,16 @@
 #include <stdlib.h>
 
 #include "common.h"
-#include <string.h>
 #include "gemm_epilogue.h"
 #include "route.h"
 #include "split16.h"
+#include "weight_image.h"
 
 namespace pvcnn {
 
 constexpr int kPbN = 256;          // points per workgroup
 constexpr int kPbK = 16;           // reduction channels per chunk = MFMA K
-
-// W (Mo, Ko) fp32 [forward: Mo = Co, Ko = Ci;  for_bwd_data: the GEMM's output channels are Ci and it reduces over Co, W'[ci][co] =
-// W[co][ci]] -> image [chunk][mtile][plane][TM rows][16 k (halves swizzled by bit 3 of the row)] bf16, TM = 32 * MB
-template <int NS>
-__device__ __forceinline__ void pw_weight_split_elem(const float *__restrict__ w, int Co, int Ci, int for_bwd_data, int TM,
-                                                     uint16_t *__restrict__ wts, long e) {
-  const int KE = for_bwd_data ? Co : Ci, ME = for_bwd_data ? Ci : Co;
-  const int chunks = ceil_div(KE, kPbK), mtiles = ceil_div(ME, TM);
-  const long total = (long)chunks * mtiles * TM * kPbK;
-  if (e >= total) return;
-  const int k_l = (int)(e % kPbK), row = (int)((e / kPbK) % TM);
-  const long rest = e / ((long)kPbK * TM);
-  const int mt = (int)(rest % mtiles), chunk = (int)(rest / mtiles);
-  const int k = chunk * kPbK + k_l, m = mt * TM + row;
-  float v = 0.0f;
-  if (k < KE && m < ME) v = for_bwd_data ? w[(size_t)k * Ci + m] : w[(size_t)m * Ci + k];
-  uint32_t p[NS];
-  split_bf16<NS>(v, p);
-  const int pos = ((k_l >> 3) ^ ((row >> 3) & 1)) * 8 + (k_l & 7);
-  const size_t blk = ((size_t)chunk * mtiles + mt) * ((size_t)NS * TM * kPbK);
-#pragma unroll
-  for (int s = 0; s < NS; ++s) wts[blk + ((size_t)s * TM + row) * kPbK + pos] = (uint16_t)p[s];
-}
-
-template <int NS>
-__global__ __launch_bounds__(256) void pw_weight_split_kernel(const float *__restrict__ w, int Co, int Ci, int for_bwd_data, int TM,
-                                                              uint16_t *__restrict__ wts) {
-  pw_weight_split_elem<NS>(w, Co, Ci, for_bwd_data, TM, wts, (long)blockIdx.x * 256 + threadIdx.x);
-}
-
-// plain-bf16 (torch.autocast) images of every registered 1x1 weight in one launch (see conv3d_weight_split_bf16_batch_kernel): an
-// entry's rows are 256-element blocks, the forward image's first
-__global__ __launch_bounds__(256) void pw_weight_split_bf16_batch_kernel(const SplitEntry *__restrict__ tab, int n) {
-  const SplitEntry e = split_entry_of(tab, n, blockIdx.x);
-  const long local = (long)(blockIdx.x - e.row_begin);
-  if (local < (long)e.rows_f) pw_weight_split_elem<1>(e.w, (int)e.Co, (int)e.Ci, 0, (int)(e.tm & 0xffffffffLL), e.wts_f, local * 256 + threadIdx.x);
-  else pw_weight_split_elem<1>(e.w, (int)e.Co, (int)e.Ci, 1, (int)(e.tm >> 32), e.wts_b, (local - (long)e.rows_f) * 256 + threadIdx.x);
-}
-
-// f16x2 image: one workgroup per (padded) output row finds the row's max |w|, scales by the power of two of scale_shift and writes the
-// fp16 hi / lo planes; wexp[row] = the shift (the epilogue scales back per output channel).
-__device__ __forceinline__ void pw_weight_split_f16_row(const float *__restrict__ w, int Co, int Ci, int for_bwd_data, int TM,
-                                                        uint16_t *__restrict__ wts, int *__restrict__ wexp, int m) {
-  const int KE = for_bwd_data ? Co : Ci, ME = for_bwd_data ? Ci : Co;
-  const int chunks = ceil_div(KE, kPbK), mtiles = ceil_div(ME, TM);
-  const int mt = m / TM, row = m - mt * TM, tid = threadIdx.x;
-  auto load = [&](int k) { return for_bwd_data ? w[(size_t)k * Ci + m] : w[(size_t)m * Ci + k]; };
-  __shared__ uint32_t red[4];
-  uint32_t mx = 0;
-  if (m < ME)
-    for (int k = tid; k < KE; k += 256) mx = max(mx, __float_as_uint(fabsf(load(k))));
-  mx = wave_max(mx);
-  if ((tid & 63) == 0) red[tid >> 6] = mx;
-  __syncthreads();
-  const int shift = scale_shift(max(max(red[0], red[1]), max(red[2], red[3])));
-  if (tid == 0) wexp[m] = shift;
-  const float scale = exp2_int(shift);
-  for (int i = tid; i < chunks * 8; i += 256) {                 // item = (chunk, channel pair)
-    const int cp = i & 7, chunk = i >> 3, k = chunk * kPbK + 2 * cp;
-    const float a = (m < ME && k < KE) ? load(k) * scale : 0.0f, b = (m < ME && k + 1 < KE) ? load(k + 1) * scale : 0.0f;
-    uint32_t p[2];
-    split_pair<2>(a, b, p);
-    const int word = ((cp >> 2) ^ ((row >> 3) & 1)) * 4 + (cp & 3);
-    uint32_t *img = reinterpret_cast<uint32_t *>(wts + ((size_t)chunk * mtiles + mt) * ((size_t)2 * TM * kPbK));
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) img[((size_t)s2 * TM + row) * 8 + word] = p[s2];
-  }
-}
-
-__global__ __launch_bounds__(256) void pw_weight_split_f16_kernel(const float *__restrict__ w, int Co, int Ci, int for_bwd_data, int TM,
-                                                                  uint16_t *__restrict__ wts, int *__restrict__ wexp) {
-  pw_weight_split_f16_row(w, Co, Ci, for_bwd_data, TM, wts, wexp, blockIdx.x);
-}
-
-// forward AND backward-data image of one weight in one launch
-__global__ __launch_bounds__(256) void pw_weight_split_f16_pair_kernel(const float *__restrict__ w, int Co, int Ci, int rows_fwd, int TM_f,
-                                                                       int TM_b, uint16_t *__restrict__ wts_f, int *__restrict__ wexp_f,
-                                                                       uint16_t *__restrict__ wts_b, int *__restrict__ wexp_b) {
-  if ((int)blockIdx.x < rows_fwd) pw_weight_split_f16_row(w, Co, Ci, 0, TM_f, wts_f, wexp_f, blockIdx.x);
-  else pw_weight_split_f16_row(w, Co, Ci, 1, TM_b, wts_b, wexp_b, blockIdx.x - rows_fwd);
-}
-
-// ... of every registered 1x1 weight of a model in one launch (see conv3d_weight_split_f16_batch_kernel)
-__global__ __launch_bounds__(256) void pw_weight_split_f16_batch_kernel(const SplitEntry *__restrict__ tab, int n) {
-  const SplitEntry e = split_entry_of(tab, n, blockIdx.x);
-  const int row = (int)(blockIdx.x - e.row_begin);
-  if (row < (int)e.rows_f) pw_weight_split_f16_row(e.w, (int)e.Co, (int)e.Ci, 0, (int)(e.tm & 0xffffffffLL), e.wts_f, e.wexp_f, row);
-  else pw_weight_split_f16_row(e.w, (int)e.Co, (int)e.Ci, 1, (int)(e.tm >> 32), e.wts_b, e.wexp_b, row - (int)e.rows_f);
-}
+static_assert(kImageK == kPbK, "weight_image.h writes the image these kernels read");
 
 // ---- epilogue of the 1x1 GEMM kernels: D[i = m][j = point]; lanes = consecutive points (128-byte rows of (B, M, N)); the rest is
 // gemm_tile_epilogue.  `lds` = the workgroup's staging buffer (>= 4 / WM * TM float pairs), free after the barrier.
@@ -175,7 +87,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16_kernel(const float *__res
   // wave owns 32*MB/2 rows x 128 points, the A traffic halves (32 KiB: 2/3 of the MFMA time) and the B fragments -- LDS reads,
   // which had headroom -- double.  Same products in the same order per output element: results are bit-identical.
   constexpr int TM = 32 * MB, WM = (MB >= 4) ? 2 : 1, MBW = MB / WM, NBW = 2 * WM;
-  constexpr int WBLK = NS * TM * kPbK;                          // bf16 elements of one (chunk, mtile) weight block
+  constexpr int WBLK = image_block<PwImage>(NS, TM);                    // bf16 elements of one (chunk, mtile) weight block
   __shared__ __attribute__((aligned(16))) uint32_t xs[NS * 8 * kPbN];       // [NS][8 channel pairs][256 points] words
 
   // XCD-aware tile order: workgroup ids go round-robin over the 8 XCDs (each with its own L2).  The mtiles workgroups that
@@ -197,7 +109,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16_kernel(const float *__res
 #pragma unroll
   for (int mb = 0; mb < MBW; ++mb) {
     const int row = (wm * MBW + mb) * 32 + j;
-    a_off[mb] = (row * 8 + ((kh ^ ((row >> 3) & 1)) * 4)) >> 2;
+    a_off[mb] = (row * 8 + ((kh ^ ((row >> 3) & 1)) * 4)) >> 2;      // (weight_image.h: row * 8 + image_half_word(row, kh), written out)
   }
   int b_pt[NBW];                                                // this lane's point inside the tile, per column block
 #pragma unroll
@@ -260,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_bf16_kernel(const float *__res
 #pragma unroll
     for (int mb = 0; mb < MBW; ++mb)
 #pragma unroll
-      for (int s = 0; s < NS; ++s) af[mb][s] = wq[s * (TM * kPbK / 8) + a_off[mb]];
+      for (int s = 0; s < NS; ++s) af[mb][s] = wq[s * (image_slab(TM) / 8) + a_off[mb]];
   };
 #pragma unroll
   for (int d = 0; d < PF; ++d) load_x(d, va_[d], vb_[d]);       // (a chunk beyond K loads zeros: c >= K)
@@ -330,7 +242,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f16_pipe_kernel(const float *_
                                                                   const uint32_t *__restrict__ x_absmax, const int *__restrict__ wexp,
                                                                   int amax_seg, ActArgs<ACT> aa) {
   static_assert(NS == 1 || NS == 2, "f16x2 or bf16");
-  constexpr int MB = 4, TM = 32 * MB, WM = 2, MBW = MB / WM, NBW = 2 * WM, WBLK = NS * TM * kPbK;
+  constexpr int MB = 4, TM = 32 * MB, WM = 2, MBW = MB / WM, NBW = 2 * WM, WBLK = image_block<PwImage>(NS, TM);
   constexpr int ITEMS = (kPbK / 2) * (kPbN / 4) / 256, TILE = NS * 8 * kPbN;
   // two tiles [plane][kh][128-point block][h][128 points][2 words], channel pair = 4 kh + 2 h + word: a staging thread owns 4 channels
   // x 4 points = two 16-byte stores of 8 consecutive words per plane; a lane's B fragment (the 8 channels 8 kh .. 8 kh + 7 of its
@@ -352,7 +264,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f16_pipe_kernel(const float *_
 #pragma unroll
   for (int mb = 0; mb < MBW; ++mb) {
     const int row = (wm * MBW + mb) * 32 + j;
-    a_off[mb] = (row * 8 + ((kh ^ ((row >> 3) & 1)) * 4)) >> 2;
+    a_off[mb] = (row * 8 + ((kh ^ ((row >> 3) & 1)) * 4)) >> 2;      // (weight_image.h: image_half_word, written out)
   }
   f32x16 acc[MBW][NBW];
 #pragma unroll
@@ -381,7 +293,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm_f16_pipe_kernel(const float *_
 #pragma unroll
     for (int mb = 0; mb < MBW; ++mb)
 #pragma unroll
-      for (int s = 0; s < NS; ++s) af[mb][s] = wq[s * (TM * kPbK / 8) + a_off[mb]];
+      for (int s = 0; s < NS; ++s) af[mb][s] = wq[s * (image_slab(TM) / 8) + a_off[mb]];
   };
   // w[s][h] = words (point 2h, pair 0), (point 2h, pair 1), (point 2h + 1, pair 0), (point 2h + 1, pair 1) of plane s
   auto convert = [&](const float4 (&va)[ITEMS], const float4 (&vb)[ITEMS], float cs, uint4 (&w)[NS][2]) {
@@ -506,7 +418,7 @@ __global__ __launch_bounds__(256, 1) void pw_gemm_f16_wide_kernel(const float *_
                                                                   int amax_seg, unsigned x_bytes, unsigned w_bytes) {
   static_assert(WMW == 2 || WMW == 4, "2 x 2 or 4 x 1 waves");
   using G = WideGeom<WMW>;
-  constexpr int NS = 2, MBW = 4, NBW = 4, TMI = 128, WBLK = NS * TMI * kPbK, TILE = G::TILE, TP = G::TP, ROWS = G::ROWS, XR = 2;
+  constexpr int NS = 2, MBW = 4, NBW = 4, TMI = 128, WBLK = image_block<PwImage>(NS, TMI), TILE = G::TILE, TP = G::TP, ROWS = G::ROWS, XR = 2;
   constexpr int HALVES = WMW == 4 ? 2 : 1;                      // 128-point halves of a 256-point tile = consecutive items
   constexpr int NROW = WMW == 4 ? 2 : 4, NPAIR = NROW / 2;      // rows / channel pairs a thread stages per step
   typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -556,7 +468,7 @@ __global__ __launch_bounds__(256, 1) void pw_gemm_f16_wide_kernel(const float *_
 
   // per-lane offsets (bytes), the same in every step
   // A fragment: row mb * 32 + j of the 128-row block (the swizzle bit is bit 3 of the row, which a multiple of 32 does not touch)
-  const uint32_t a_off = (uint32_t)(j * 8 + ((kh ^ ((j >> 3) & 1)) * 4)) * 4u;
+  const uint32_t a_off = (uint32_t)(j * 8 + ((kh ^ ((j >> 3) & 1)) * 4)) * 4u;      // (weight_image.h: image_half_word, written out)
   // staging item of a thread.  WMW = 2: channel pairs 2 wave, 2 wave + 1 (words 2 (wave & 1) + {0, 1} of half kh' = wave >> 1) of
   // point quad `lane` (64 quads).  WMW = 4: channel pair p = lane & 7 (word p & 3 of half p >> 2) of point quad 8 wave + (lane >> 3)
   // (32 quads): a wave instruction reads 128-byte runs of 8 rows
@@ -600,7 +512,7 @@ __global__ __launch_bounds__(256, 1) void pw_gemm_f16_wide_kernel(const float *_
   };
   // plane 0 = hi, plane 1 = lo (split_pair)
   auto load_a1 = [&](uint32_t soff, int plane, int mb) {
-    return __builtin_amdgcn_raw_buffer_load_b128(wrsrc, a_off + (uint32_t)(plane * (TMI * kPbK * 2) + mb * 1024), soff, 0);
+    return __builtin_amdgcn_raw_buffer_load_b128(wrsrc, a_off + (uint32_t)(plane * (image_slab(TMI) * 2) + mb * 1024), soff, 0);
   };
   auto load_b1 = [&](int buf, int plane, int nb) {
     return *reinterpret_cast<const u32x4 *>(xs8 + (buf * TILE + plane * 2 * TP * 4) * 4 + b_off + nb * 512);
@@ -795,106 +707,33 @@ __global__ __launch_bounds__(256, 1) void pw_gemm_f16_wide_kernel(const float *_
   PVCNN_PROBE_END();
 }
 
-using route::pb_mb;
 static_assert(route::kNumCU == kNumCU && route::kPbN == kPbN, "route.h plans with this file's constants");
 
 }  // namespace pvcnn
 
 using namespace pvcnn;
 
-static size_t pb_image_bytes(int KE, int ME, int nsplit) {
-  const int TM = 32 * pb_mb(ME);
-  return (size_t)ceil_div(KE, kPbK) * ceil_div(ME, TM) * nsplit * TM * kPbK * sizeof(uint16_t);
-}
-
-// nsplit: 1 = bf16, 3 = bf16x3, 2 = f16x2 (image followed by one int32 shift per padded output channel)
+// ---- the weight images: all of it is weight_image.h on PwImage ----
 extern "C" size_t pvcnn_pwconv_weight_split_bytes(int Co, int Ci, int for_bwd_data, int nsplit) {
-  if (Co <= 0 || Ci <= 0 || nsplit < 1 || nsplit > 3) return 0;
-  const int KE = for_bwd_data ? Co : Ci, ME = for_bwd_data ? Ci : Co;
-  const int TM = 32 * pb_mb(ME);
-  return pb_image_bytes(KE, ME, nsplit) + (nsplit == 2 ? (size_t)ceil_div(ME, TM) * TM * sizeof(int) : 0);
+  return weight_split_bytes<PwImage>(Co, Ci, for_bwd_data, nsplit);
 }
-
 extern "C" int pvcnn_pwconv_weight_split(const float *w, int Co, int Ci, int for_bwd_data, int nsplit, void *wts, void *stream) {
-  PVCNN_REQUIRE(w && wts && Co > 0 && Ci > 0, "bad argument");
-  PVCNN_REQUIRE(nsplit >= 1 && nsplit <= 3, "nsplit must be 1 (bf16), 2 (f16x2) or 3 (bf16x3)");
-  PVCNN_REQUIRE(aligned16(wts), "wts must be 16-byte aligned");
-  const int KE = for_bwd_data ? Co : Ci, ME = for_bwd_data ? Ci : Co;
-  const int TM = 32 * pb_mb(ME);
-  if (nsplit == 2) {
-    int *wexp = reinterpret_cast<int *>(static_cast<char *>(wts) + pb_image_bytes(KE, ME, 2));
-    hipLaunchKernelGGL(pw_weight_split_f16_kernel, dim3(ceil_div(ME, TM) * TM), dim3(256), 0, static_cast<hipStream_t>(stream), w, Co, Ci,
-                       for_bwd_data, TM, static_cast<uint16_t *>(wts), wexp);
-    return check_launch("pwconv_weight_split_f16");
-  }
-  const long total = (long)ceil_div(KE, kPbK) * ceil_div(ME, TM) * TM * kPbK;
-  const dim3 grid((unsigned)((total + 255) / 256));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (nsplit == 1) hipLaunchKernelGGL(pw_weight_split_kernel<1>, grid, dim3(256), 0, s, w, Co, Ci, for_bwd_data, TM, static_cast<uint16_t *>(wts));
-  else             hipLaunchKernelGGL(pw_weight_split_kernel<3>, grid, dim3(256), 0, s, w, Co, Ci, for_bwd_data, TM, static_cast<uint16_t *>(wts));
-  return check_launch("pwconv_weight_split");
+  return weight_split<PwImage>(w, Co, Ci, for_bwd_data, nsplit, wts, stream);
 }
-
-// both f16x2 images of w (forward + backward-data) in one launch; buffers sized by pvcnn_pwconv_weight_split_bytes(.., 0 / 1, 2)
 extern "C" int pvcnn_pwconv_weight_split_pair(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, void *stream) {
-  PVCNN_REQUIRE(w && wts_fwd && wts_bwd && Co > 0 && Ci > 0, "bad argument");
-  PVCNN_REQUIRE(aligned16(wts_fwd) && aligned16(wts_bwd), "images must be 16-byte aligned");
-  const int TM_f = 32 * pb_mb(Co), TM_b = 32 * pb_mb(Ci);
-  const int rows_f = ceil_div(Co, TM_f) * TM_f, rows_b = ceil_div(Ci, TM_b) * TM_b;
-  int *wexp_f = reinterpret_cast<int *>(static_cast<char *>(wts_fwd) + pb_image_bytes(Ci, Co, 2));
-  int *wexp_b = reinterpret_cast<int *>(static_cast<char *>(wts_bwd) + pb_image_bytes(Co, Ci, 2));
-  hipLaunchKernelGGL(pw_weight_split_f16_pair_kernel, dim3(rows_f + rows_b), dim3(256), 0, static_cast<hipStream_t>(stream), w, Co, Ci, rows_f,
-                     TM_f, TM_b, static_cast<uint16_t *>(wts_fwd), wexp_f, static_cast<uint16_t *>(wts_bwd), wexp_b);
-  return check_launch("pwconv_weight_split_pair");
+  return weight_split_pair<PwImage>(w, Co, Ci, wts_fwd, wts_bwd, stream);
 }
-
-// batched form of pvcnn_pwconv_weight_split_pair (see pvcnn_conv3d_weight_split_pair_entry / _batch)
 extern "C" long pvcnn_pwconv_weight_split_pair_entry(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, long long *entry) {
-  if (!w || !wts_fwd || !wts_bwd || !entry || Co <= 0 || Ci <= 0 || !aligned16(wts_fwd) || !aligned16(wts_bwd)) return -1;
-  const int TM_f = 32 * pb_mb(Co), TM_b = 32 * pb_mb(Ci);
-  const int rows_f = ceil_div(Co, TM_f) * TM_f, rows_b = ceil_div(Ci, TM_b) * TM_b;
-  SplitEntry e;
-  e.w = w;
-  e.wts_f = static_cast<uint16_t *>(wts_fwd);
-  e.wexp_f = reinterpret_cast<int *>(static_cast<char *>(wts_fwd) + pb_image_bytes(Ci, Co, 2));
-  e.wts_b = static_cast<uint16_t *>(wts_bwd);
-  e.wexp_b = reinterpret_cast<int *>(static_cast<char *>(wts_bwd) + pb_image_bytes(Co, Ci, 2));
-  e.Co = Co; e.Ci = Ci; e.rows_f = rows_f; e.tm = (long long)TM_f | ((long long)TM_b << 32); e.row_begin = 0;
-  memcpy(entry, &e, sizeof(e));
-  return rows_f + rows_b;
+  return weight_split_pair_entry<PwImage>(w, Co, Ci, wts_fwd, wts_bwd, entry, 2);
 }
-
 extern "C" int pvcnn_pwconv_weight_split_pair_batch(const void *table, int n, long total_rows, void *stream) {
-  PVCNN_REQUIRE(n >= 0 && total_rows >= 0 && total_rows <= 0x7fffffffL, "bad size");
-  if (n == 0 || total_rows == 0) return 0;
-  PVCNN_REQUIRE(table && (reinterpret_cast<uintptr_t>(table) & 7) == 0, "null or misaligned table");
-  hipLaunchKernelGGL(pw_weight_split_f16_batch_kernel, dim3((unsigned)total_rows), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const SplitEntry *>(table), n);
-  return check_launch("pwconv_weight_split_pair_batch");
+  return weight_split_pair_batch<PwImage>(table, n, total_rows, stream, 2);
 }
-
-// ... and of the plain-bf16 images (nsplit = 1; buffers sized by pvcnn_pwconv_weight_split_bytes(.., 0 / 1, 1))
 extern "C" long pvcnn_pwconv_weight_split_pair_entry_bf16(const float *w, int Co, int Ci, void *wts_fwd, void *wts_bwd, long long *entry) {
-  if (!w || !wts_fwd || !wts_bwd || !entry || Co <= 0 || Ci <= 0 || !aligned16(wts_fwd) || !aligned16(wts_bwd)) return -1;
-  const int TM_f = 32 * pb_mb(Co), TM_b = 32 * pb_mb(Ci);
-  const long blocks_f = ((long)ceil_div(Ci, kPbK) * ceil_div(Co, TM_f) * TM_f * kPbK + 255) / 256;
-  const long blocks_b = ((long)ceil_div(Co, kPbK) * ceil_div(Ci, TM_b) * TM_b * kPbK + 255) / 256;
-  SplitEntry e;
-  e.w = w;
-  e.wts_f = static_cast<uint16_t *>(wts_fwd); e.wexp_f = nullptr;
-  e.wts_b = static_cast<uint16_t *>(wts_bwd); e.wexp_b = nullptr;
-  e.Co = Co; e.Ci = Ci; e.rows_f = blocks_f; e.tm = (long long)TM_f | ((long long)TM_b << 32); e.row_begin = 0;
-  memcpy(entry, &e, sizeof(e));
-  return blocks_f + blocks_b;
+  return weight_split_pair_entry<PwImage>(w, Co, Ci, wts_fwd, wts_bwd, entry, 1);
 }
-
 extern "C" int pvcnn_pwconv_weight_split_pair_batch_bf16(const void *table, int n, long total_rows, void *stream) {
-  PVCNN_REQUIRE(n >= 0 && total_rows >= 0 && total_rows <= 0x7fffffffL, "bad size");
-  if (n == 0 || total_rows == 0) return 0;
-  PVCNN_REQUIRE(table && (reinterpret_cast<uintptr_t>(table) & 7) == 0, "null or misaligned table");
-  hipLaunchKernelGGL(pw_weight_split_bf16_batch_kernel, dim3((unsigned)total_rows), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const SplitEntry *>(table), n);
-  return check_launch("pwconv_weight_split_pair_batch_bf16");
+  return weight_split_pair_batch<PwImage>(table, n, total_rows, stream, 1);
 }
 
 extern "C" size_t pvcnn_pwconv_fwd_split_stats_parts(int B, int N) {
@@ -930,7 +769,8 @@ static int pwconv_fwd_split_impl(const float *x, const void *wts, const float *b
   const uint16_t *w16 = static_cast<const uint16_t *>(wts);
   float2 *sp = reinterpret_cast<float2 *>(stats_part);
   const uint32_t *am = static_cast<const uint32_t *>(x_absmax);
-  const int *wexp = nsplit == 2 ? reinterpret_cast<const int *>(static_cast<const char *>(wts) + pb_image_bytes(K, M, 2)) : nullptr;
+  const ImageGeom<PwImage> image(M, K, false);                  // (a backward-data call names the image's own rows and depth)
+  const int *wexp = nsplit == 2 ? image.shifts(wts) : nullptr;
 #define PVCNN_PB_LAUNCH(KERNEL, LDS, ...) \
   hipLaunchKernelGGL((KERNEL), grid, dim3(256), LDS, s, x, w16, bias, y, K, M, N, p.tiles_n, (int)p.tiles_total, sp, am, wexp, amax_seg, ##__VA_ARGS__)
 #define PVCNN_PB_GEMM(NSV, MBV, PFV)                                                                \
@@ -940,7 +780,7 @@ static int pwconv_fwd_split_impl(const float *x, const void *wts, const float *b
   } while (0)
   switch (p.kernel) {
     case route::PwKernel::Wide: if constexpr (!ACT) {
-      const unsigned xb = (unsigned)((size_t)B * K * N * 4), wb = (unsigned)pb_image_bytes(K, M, 2);
+      const unsigned xb = (unsigned)((size_t)B * K * N * 4), wb = (unsigned)image.image_bytes(2);
 #define PVCNN_WIDE_LAUNCH(ABV)                                                                      \
       do {                                                                                          \
         if (p.wmw == 4) PVCNN_PB_LAUNCH((pw_gemm_f16_wide_kernel<4, ABV>), WideGeom<4>::LDS, xb, wb);  \

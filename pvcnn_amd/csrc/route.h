@@ -18,7 +18,7 @@ constexpr int kCoTileB = 64;       // Conv3d: output channels (weight rows) per 
 constexpr int kKc = 16;            // Conv3d: input channels per chunk
 constexpr int kPbN = 256;          // 1x1 GEMM: points per workgroup tile
 
-inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
 // ---- Conv3d -----------------------------------------------------------------------------------------------------------------------
 
@@ -98,7 +98,7 @@ inline ConvFwdPlan conv3d_fwd_split_plan(int B, int Ci, int Co, int R, int nspli
 
 // ---- 1x1 GEMM ---------------------------------------------------------------------------------------------------------------------
 
-inline int pb_mb(int M) { return M > 64 ? 4 : 2; }     // 32-row blocks of a weight tile (and of the weight image's row padding)
+constexpr int pb_mb(int M) { return M > 64 ? 4 : 2; }     // 32-row blocks of a weight tile (and of the weight image's row padding)
 
 enum class PwKernel {
   Gemm,   // pw_gemm_bf16_kernel<nsplit, mb, pf, vec>
