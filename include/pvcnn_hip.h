@@ -242,6 +242,53 @@ PVCNN_API int pvcnn_batch_frustum_rgb(const float *rows, const int64_t *offsets,
                             int N, const int32_t *choices, const int64_t *seed, float *features, float *one_hot_vectors,
                             float *rotation_angle, double *rgb_score, void *stream);
 
+/* ---- augmentation of an assembled batch (pvcnn_amd/augment.py, csrc/augment.hip; an additive group: the ABI version does not
+ * move) -------------------------------------------------------------------------------------------------------------
+ * NOT in the reference (its datasets draw what pvcnn_batch_* draw): the usual transforms of point-cloud training -- a rotation about
+ * an axis, a rotation perturbation, axis flips, scale, translation, clipped Gaussian jitter, PointNet++'s random point dropout -- as
+ * two launches that never allocate.  Every pointer is device memory except `layout`.
+ *
+ * pvcnn_augment_draw: params (B, PVCNN_AUGMENT_PARAMS = 24) fp64, one row per cloud, from a Philox4x32-10 stream keyed by `seed` (two
+ * int64 words in device memory: key, stream id -- the convention of pvcnn_batch_*; the counters differ, so one pair of words may key
+ * an assembly and its augmentation).  Row: [0:9] the matrix Rp row-major, [9] scale s, [10:13] translation t, [13] dropout ratio,
+ * [14:18] the raw angles theta, a, b, c, [18:21] the three flip uniforms, [21:24] zeros.
+ *   theta ~ U(-rot_max, rot_max) about `axis` (0: x, 1: y, 2: z);  a, b, c = clip(perturb_sigma z, +-perturb_clip), z standard normal;
+ *   axis k is flipped when u_k < flip_k;  s ~ U(scale_lo, scale_hi);  t ~ U(-translate_max, translate_max)^3;  ratio = u drop_max.
+ *   Rp = Rx(a) Ry(b) Rz(c) R_axis(theta) diag(+-1), right-handed rotations, composed in fp64.
+ * A range that is off gives that stage's identity exactly: rot_max = 0 -> theta = 0.0, perturb_sigma = 0 -> a = b = c = 0.0 (with both
+ * Rp is a 0 / 1 matrix, +-1 with flips), scale_lo = scale_hi = 1 -> s = 1.0, translate_max = 0 -> t = 0.0, drop_max = 0 -> ratio = 0.0.
+ *
+ * pvcnn_augment_apply: src (B, C, N) fp32 -> dst (B, C, N) fp32, out of place; the C * N floats of a sample are contiguous, samples
+ * are *_batch_stride elements apart (>= C * N; ignored for B = 1).  targets_src / targets_dst (B, N) int64 with batch strides of
+ * their own: both or neither.  `layout` (HOST memory, read before the call returns): num_triples <= 4 pairs (role, first plane);
+ * the planes (c, c + 1, c + 2) of a PVCNN_AUGMENT_POSITION triple become y = s (Rp x) + t + jitter, those of a
+ * PVCNN_AUGMENT_DIRECTION triple y = Rp x (normals); every other plane is copied.  Triples beyond C or overlapping are refused.
+ *   jitter (jitter_on): per point and axis clip(jitter_sigma z, +-jitter_clip); z from `jitter` (B, 3, N) fp32 when given (PARITY
+ *   MODE), else from the Philox stream of `seed` (Box-Muller, fp32).
+ *   dropout (drop_on): point n > 0 is dropped when u[b, n] <= ratio[b] (params column 13); u from `keep` (B, N) fp32 when given, else
+ *   from the stream.  A dropped point takes point 0's TRANSFORMED planes in all C channels (point 0's own jitter draw) and point 0's
+ *   target -- PointNet++'s pc[drop_idx] = pc[0] after the fact.
+ *   jitter_out (B, 3, N), keep_out (B, N) fp32, optional: every point's own draws (a dropped point uses point 0's jitter row).
+ * Arithmetic: each element in fp64 from the fp32 input, r = (Rp[k][0] x0 + Rp[k][1] x1) + Rp[k][2] x2, y = (s r + t[k]) + jitter[k],
+ * no fused multiply-add, rounded once to fp32.
+ * Aliasing: dst may be src (the same address and batch stride) when drop_on = 0 only; any other overlap, and any aliasing with
+ * dropout on, is refused (a dropped point reads point 0 while another thread writes it).  Likewise the targets.
+ * 16-byte accesses when N % 4 == 0 and every base and batch stride is 16-byte aligned, scalar ones otherwise: the same bits.
+ * C * N <= 2^31 - 1; sample addressing is 64-bit; the grid strides over N and B. */
+#define PVCNN_AUGMENT_PARAMS 24
+#define PVCNN_AUGMENT_MAX_TRIPLES 4
+#define PVCNN_AUGMENT_POSITION 1
+#define PVCNN_AUGMENT_DIRECTION 2
+PVCNN_API int pvcnn_augment_draw(int B, int axis, double rot_max, double perturb_sigma, double perturb_clip, double flip_x,
+                       double flip_y, double flip_z, double scale_lo, double scale_hi, double translate_max, double drop_max,
+                       const int64_t *seed, double *params, void *stream);
+PVCNN_API int pvcnn_augment_apply(const float *src, long long src_batch_stride, const int64_t *targets_src,
+                        long long targets_src_batch_stride, int B, int C, int N, const int32_t *layout, int num_triples,
+                        const double *params, double jitter_sigma, double jitter_clip, int jitter_on, int drop_on,
+                        const float *jitter, const float *keep, const int64_t *seed, float *dst, long long dst_batch_stride,
+                        int64_t *targets_dst, long long targets_dst_batch_stride, float *jitter_out, float *keep_out,
+                        void *stream);
+
 /* ---- 3-nearest-neighbour interpolation ----------------------------------------------------
  * replaces three_nearest_neighbors_interpolate_forward/backward
  *          (interpolate/neighbor_interpolate.cpp:6-65, neighbor_interpolate.cu:20-170)

@@ -186,6 +186,10 @@ SIGNATURES = {
     'pvcnn_frame_pack': (_i, [_vp, _ll, _vp, _vp, _vp, _i, _vp, _vp, _ll, _ll, _vp, _vp, _vp]),
     'pvcnn_frame_batch': (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d] + [_vp] * 8),
     'pvcnn_frame_rotate_rows': (_i, [_vp, _ll, _vp, _ll, _vp, _vp]),
+    # augmentation of an assembled batch (csrc/augment.hip): the per-cloud draws, then one pass over the batch
+    'pvcnn_augment_draw': (_i, [_i, _i] + [_d] * 10 + [_vp, _vp, _vp]),
+    'pvcnn_augment_apply': (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _vp, _i, _vp, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp,
+                                 _vp]),
 }
 
 _lib = None

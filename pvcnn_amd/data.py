@@ -22,6 +22,7 @@ against.  The product path (`assemble`, `DeviceLoader.feed`) needs device tensor
 import numpy as np
 import torch
 
+from . import augment as _augment
 from .modules.functional import backend as _seam
 
 __all__ = ['DeviceS3DIS', 'DeviceShapeNet', 'DeviceFrustumKitti', 'DeviceLoader']
@@ -625,13 +626,23 @@ class DeviceLoader:
             loader.new_epoch()
             for _ in range(len(loader)): step()
 
-    `rank` / `world_size` keep every world_size-th item of the permutation (a data-parallel rank's share)."""
+    `rank` / `world_size` keep every world_size-th item of the permutation (a data-parallel rank's share).
 
-    def __init__(self, store, batch_size, shuffle=True, drop_last=False, generator=None, rank=0, world_size=1):
+    `augment` (an `augment.Augment`; S3DIS and ShapeNet stores): every batch is assembled into a private staging batch and augmented
+    from there into the batch handed out -- features and targets, two more launches per `feed()`, captured with the step and keyed
+    by the same seed words as the assembly.  Without it nothing changes: the same launches, the same tensors, the same bits."""
+
+    def __init__(self, store, batch_size, shuffle=True, drop_last=False, generator=None, rank=0, world_size=1, augment=None):
         if int(batch_size) < 1:
             raise ValueError('batch_size must be positive')
         if not 0 <= int(rank) < int(world_size):
             raise ValueError('rank must lie in [0, world_size)')
+        if augment is not None:
+            if isinstance(store, DeviceFrustumKitti):
+                raise ValueError('a Frustum-KITTI store cannot be augmented: its targets hold box geometry (centre, heading, size) that '
+                                 'a generic transform of the points would silently invalidate; the dataset has its own flip and shift')
+            augment.check_channels(store.out_channels)
+        self.augment, self._staging, self._augment_params = augment, None, None
         self.store, self.batch_size, self.shuffle, self.drop_last = store, int(batch_size), bool(shuffle), bool(drop_last)
         self.generator, self.rank, self.world_size = generator, int(rank), int(world_size)
         self.num_items = len(range(self.rank, len(store), self.world_size))
@@ -669,10 +680,18 @@ class DeviceLoader:
         a graph capture (the `loss_fn` of GraphedTrainStep) it is captured with the step; that needs drop_last=True -- the ragged last
         batch of drop_last=False goes through `__iter__` and the step's eager path."""
         out = self.static_batch()
-        if choices is None and seed is None:
+        if seed is None and (choices is None or self.augment is not None):
             seed = self.seed.random_(0, 2 ** 62)                 # torch's device generator: fresh words on every replay
-        self.store.assemble(None, out, choices=choices, jitter=jitter, flip=flip, shift=shift, seed=seed, order=self.order,
+        into = out
+        if self.augment is not None:
+            if self._staging is None:
+                self._staging = self.store.empty_batch(self.batch_size)
+                self._augment_params = torch.empty((self.batch_size, _augment.PARAMS), dtype=torch.float64, device=self.store.device)
+            into = self._staging
+        self.store.assemble(None, into, choices=choices, jitter=jitter, flip=flip, shift=shift, seed=seed, order=self.order,
                             cursor=self.cursor, batch_size=self.batch_size)
+        if self.augment is not None:
+            self.augment.augment(into[0], into[1], out=out[0], out_targets=out[1], seed=seed, params_out=self._augment_params)
         self.cursor.add_(self.batch_size)
         return out
 
@@ -680,5 +699,7 @@ class DeviceLoader:
         self.new_epoch()
         for size in self.batch_sizes():
             batch = self.store.assemble(None, None, order=self.order, cursor=self.cursor, batch_size=size)
+            if self.augment is not None:
+                batch = self.augment.augment(batch[0], batch[1])
             self.cursor.add_(size)
             yield batch

@@ -228,6 +228,29 @@ class HipBackend:
         _dev(ref, entry)
         _run(getattr(self.lib, 'pvcnn_' + entry), entry, ref, *(a if a is None or isinstance(a, torch.Tensor) else int(a) for a in args))
 
+    # ---- augmentation of an assembled batch (csrc/augment.hip; pvcnn_amd/augment.py checks shapes and owns the tensors) ----------
+    has_augment = True
+
+    def augment_draw(self, params, seed, axis, scalars):
+        """params (B, 24) fp64 <- the per-cloud draws; `scalars`: the ten ranges of pvcnn_augment_draw in the header's order."""
+        _run(self.lib.pvcnn_augment_draw, 'augment_draw', params, params.shape[0], int(axis), *(float(v) for v in scalars), seed, params)
+
+    def augment_apply(self, src, targets_src, layout, params, jitter_sigma, jitter_clip, jitter_on, drop_on, jitter, keep, seed, dst,
+                      targets_dst, jitter_out, keep_out):
+        """One pvcnn_augment_apply launch.  src / dst (B, C, N) fp32 may be batch-strided views, and so may the targets (B, N) int64,
+        whose rows the caller has checked to be contiguous; `layout`: [(role, first plane), ...] with the header's role numbers (it
+        goes as a small host array)."""
+        b, c, n = src.shape
+        stride_x = _f32_rows(src, 'src'), _f32_rows(dst, 'dst')
+        stride_t = (n, n)
+        if targets_src is not None:
+            _dev(targets_src, 'targets'); _dev(targets_dst, 'out_targets')
+            stride_t = tuple(t.stride(0) if b > 1 else n for t in (targets_src, targets_dst))
+        flat = (ctypes.c_int32 * max(2 * len(layout), 1))(*[v for pair in layout for v in pair])
+        _run(self.lib.pvcnn_augment_apply, 'augment_apply', src, src, stride_x[0], targets_src, stride_t[0], b, c, n, flat, len(layout),
+             params, float(jitter_sigma), float(jitter_clip), int(jitter_on), int(drop_on), jitter, keep, seed, dst, stride_x[1],
+             targets_dst, stride_t[1], jitter_out, keep_out)
+
     # ---- ball_query.cpp:6-30 ----------------------------------------------------------------
     def ball_query(self, centers_coords, points_coords, radius, num_neighbors):
         _f32(centers_coords, 'centers_coords'); _f32(points_coords, 'points_coords')
