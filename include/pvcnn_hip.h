@@ -1069,6 +1069,63 @@ PVCNN_API int pvcnn_frame_batch(const float *rows, long long cap, const unsigned
 PVCNN_API int pvcnn_frame_rotate_rows(float *rows, long long R, const long long *offsets, long long W, const double *cos_sin,
                                       void *stream);
 
+/* ---- KITTI frame store: Frustum-KITTI training batches cut out of the frames, with a fresh perturbation of every sample's 2-D box
+ * (csrc/frame_store.hip, pvcnn_amd/frame_store.py; an additive group: the ABI version does not move).  The original preparation
+ * (frustum-pointnets' extract_frustum_data, perturb_box2d) draws five perturbed copies of every ground-truth box once, offline; here the
+ * draw is made per sample when the batch is assembled.  THIS is the definition, restated in numpy by tests/frame_store_truth.py: fp64,
+ * one rounding per operation, left to right.
+ *
+ * The store: `rows` (R, 4) fp32 and `uv` (R, 2) fp64 of the IN-IMAGE points of every frame (pvcnn_frame_project's outputs, the points
+ * with in_image = 0 left out, ascending point index), frame f owning rows frame_offsets[f] .. frame_offsets[f + 1] (at most
+ * max_frame_points <= PVCNN_FRAME_STORE_MAX_POINTS of them: it sizes the launch's LDS, pvcnn_frame_store_lds_bytes).  An item is one
+ * object: item_f64 (W, PVCNN_FRAME_STORE_ITEM_COLUMNS), every trigonometric scalar from the host:
+ *   [0..2] P[0,0] P[0,2] P[0,3]   [3..6] xmin ymin xmax ymax   [7..9] h w l   [10..12] tx ty tz   [13, 14] cos ry, sin ry   [15] ry
+ *   [16..18] the centre (corner 0 + corner 6) / 2, not rotated   [19] rotation_angle = pi / 2 + frustum_angle of the stored box
+ *   [20, 21] its cos, sin   [22, 23] zero;
+ * item_f32 (W, K + 3): one-hot, size residual;  item_i64 (W, 3): frame, size template id, class id.
+ * Sample b is item order[cursor[0] + b], as pvcnn_batch_* read it; items, frames, offsets and parity choices are clamped to the store.
+ *
+ * Box perturbation, r = shift_ratio, four uniforms u0..u3 in [0, 1) (the original's random_shift_box2d, its draws in its order):
+ *   w = xmax - xmin;  h = ymax - ymin;  cx = (xmin + xmax) / 2;  cy = (ymin + ymax) / 2
+ *   cx2 = cx + (w r) (u0 2 - 1);  cy2 = cy + (h r) (u1 2 - 1);  h2 = h ((1 + (u2 2) r) - r);  w2 = w ((1 + (u3 2) r) - r)
+ *   box' = (cx2 - w2 / 2, cy2 - h2 / 2, cx2 + w2 / 2, cy2 + h2 / 2)
+ *   rotation_angle' = pi / 2 + (-atan2(20, X)),  X = ((cu - P02) 20) / P00 + P03 / (-P00),  cu = (xmin' + xmax') / 2.
+ * shift_ratio == 0: no perturbation -- no draw is consumed, the stored box and the host's angle are used, used = 0.
+ * Selection: point in box = u >= xmin & u < xmax & v >= ymin & v < ymax on the stored uv; positive = selected & inside the 3-D box by
+ * the box-frame test of pvcnn_frame_count on the stored fp32 row.  The perturbed box is used iff ymax' - ymin' >= min_box_height and it
+ * selects a positive point (used = 1); otherwise the item's stored box with the host's angle, cos and sin (used = 0).
+ * Of the k selected points of the box used, position p of N takes choices[b][p] clamped to [0, k) or
+ * mulhi(Philox4x32-10(counter (p, b, lo32 seed[1], 0), key seed[0]).x, k), as pvcnn_frame_batch; k == 0 yields zeros.
+ * mask_logits = the box-frame test of the picked row.  With frustum_rotate: the row as pvcnn_frame_batch rotates it
+ * (x' = fp32(x c + z (-s)), z' = fp32(x s + z c)), the centre cx' = cx c + cz (-s), cz' = cx s + cz c, heading = ry - rotation_angle
+ * (c, s, rotation_angle of the box used); without it, rows, centre and heading = ry stay.  dist = sqrt(c0 c0 + c1 c1) of that centre
+ * (the reference's expression as written); heading bin and residual = pvcnn_amd.data.angle_to_bin_id of heading, or of pi - heading
+ * when flipped (% is numpy's: fmod, plus the divisor when the remainder is non-zero and negative); flip and shift are those of
+ * pvcnn_batch_frustum, the same draws (counter (0, b, stream, 2)) and the same arithmetic.
+ *
+ * PARITY MODE (`choices` given): `params` (B, PVCNN_FRAME_STORE_PARAMS) fp64 rows [0..3] u0..u3, [4..7] the perturbed box,
+ * [8] rotation_angle', [9, 10] its cos, sin, [11] zero -- required when shift_ratio != 0; the box and the angle are TAKEN from the row
+ * (no trigonometric function runs on the device); `flip` / `shift` (B) fp64 as pvcnn_batch_frustum.  params, flip or shift without
+ * choices are refused.  DEVICE MODE: u_j = word j of Philox4x32-10(counter (0, b, lo32 seed[1], 3), key seed[0]) times 2^-32 -- counter
+ * word 3 = 3 is used by no other draw of the input side (0: choices, 1: ShapeNet's jitter, 2: flip and shift); cos and sin of
+ * rotation_angle' are the device's fp64 library functions.  Optional outputs in both modes: params_out (B, 12) the rows used, `used`
+ * (B) int32, choices_out (B, N) int32, flip_out (B) fp64 (1 / 0), shift_out (B) fp64 (the normal draw) -- fed back in parity mode
+ * they reproduce the batch bit for bit.  Outputs as pvcnn_batch_frustum.  One launch; never allocates, synchronises or uses an atomic. */
+#define PVCNN_FRAME_STORE_PARAMS 12
+#define PVCNN_FRAME_STORE_ITEM_COLUMNS 24
+#define PVCNN_FRAME_STORE_MAX_POINTS 131072
+PVCNN_API size_t pvcnn_frame_store_lds_bytes(long long max_frame_points);
+PVCNN_API int pvcnn_frame_store_batch(const float *rows, const double *uv, const int64_t *frame_offsets, long long F, long long R,
+                                      long long max_frame_points, const double *item_f64, const float *item_f32,
+                                      const int64_t *item_i64, long long W, int K, int num_heading_angle_bins, int frustum_rotate,
+                                      int random_flip, int random_shift, double shift_ratio, double min_box_height,
+                                      const int64_t *order, long long order_len, const int64_t *cursor, int B, int N,
+                                      const double *params, const int32_t *choices, const double *flip, const double *shift,
+                                      const int64_t *seed, float *features, float *one_hot_vectors, int64_t *mask_logits, float *center,
+                                      int64_t *heading_bin_id, float *heading_residual, int64_t *size_template_id, float *size_residual,
+                                      int64_t *class_id, double *params_out, int32_t *used, int32_t *choices_out, double *flip_out,
+                                      double *shift_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

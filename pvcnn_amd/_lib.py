@@ -186,6 +186,9 @@ SIGNATURES = {
     'pvcnn_frame_pack': (_i, [_vp, _ll, _vp, _vp, _vp, _i, _vp, _vp, _ll, _ll, _vp, _vp, _vp]),
     'pvcnn_frame_batch': (_i, [_vp, _ll, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d] + [_vp] * 8),
     'pvcnn_frame_rotate_rows': (_i, [_vp, _ll, _vp, _ll, _vp, _vp]),
+    # Frustum-KITTI batches cut out of the frames, with a perturbed 2-D box per sample (csrc/frame_store.hip)
+    'pvcnn_frame_store_lds_bytes': (_sz, [_ll]),
+    'pvcnn_frame_store_batch': (_i, [_vp] * 3 + [_ll] * 3 + [_vp] * 3 + [_ll] + [_i] * 5 + [_d] * 2 + [_vp, _ll, _vp, _i, _i] + [_vp] * 20),
     # augmentation of an assembled batch (csrc/augment.hip): the per-cloud draws, then one pass over the batch
     'pvcnn_augment_draw': (_i, [_i, _i] + [_d] * 10 + [_vp, _vp, _vp]),
     'pvcnn_augment_apply': (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _vp, _i, _vp, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp,

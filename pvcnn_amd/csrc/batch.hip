@@ -66,13 +66,6 @@ __device__ __forceinline__ uint2 batch_key(const BatchStore &s) {
   return make_uint2((uint32_t)s.seed[0], (uint32_t)((uint64_t)s.seed[0] >> 32));
 }
 
-// a standard normal pair from two random words (Box-Muller, fp32): u1 in (0, 1], u2 in [0, 1)
-__device__ __forceinline__ float2 batch_normal2(uint32_t r1, uint32_t r2) {
-  const float u1 = (float)((r1 >> 8) + 1u) * 0x1p-24f, u2 = (float)(r2 >> 8) * 0x1p-24f;
-  const float rad = sqrtf(-2.0f * logf(u1)), ang = 6.283185307179586f * u2;
-  return make_float2(rad * cosf(ang), rad * sinf(ang));
-}
-
 // words[0 .. N) <- N distinct of n in random order (low halves); npad = n rounded up to a power of two <= kBatchMaxSort
 __device__ __forceinline__ void batch_sort_select(unsigned long long *words, int n, int b, uint32_t stream, uint2 key) {
   int npad = 1;

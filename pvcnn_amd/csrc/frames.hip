@@ -11,15 +11,14 @@
 // lanes' bits (ascending point index: numpy's boolean indexing), and "the k-th selected point of box m" is a binary search of the
 // tile prefix followed by a select-k-th-bit of one word -- no sort, no compaction pass over the scan.
 #include "common.h"
+#include "frame_tiles.h"
 #include "philox.h"
 
 namespace pvcnn {
 
-constexpr int kFrameTile = PVCNN_FRAME_TILE;   // points per tile = lanes per wave
 constexpr int kFrameThreads = 256;             // 4 tiles per workgroup
 constexpr int kFrameCols = PVCNN_FRAME_BOX_COLUMNS;
 constexpr long long kFrameMaxPoints = 1ll << 30;
-static_assert(kFrameTile == kWave, "a tile is one wave");
 
 __device__ __forceinline__ long long frame_points(long long cap, long long n, const int *count) {
   if (count) n = count[0];
@@ -150,18 +149,6 @@ __global__ __launch_bounds__(kFrameThreads) void frame_pack_kernel(const float4 
   if (i >= cap || first < 0 || dst >= offsets[w + 1] || dst >= R) return;       // never outside the caller's tables
   out_rows[dst] = rows[i];
   if (out_labels) out_labels[dst] = label_mask ? (unsigned char)((label_mask[(size_t)m * tiles + tile] >> lane) & 1ull) : 0;
-}
-
-// the position of the r-th (from 0) set bit of a word that has more than r of them
-__device__ __forceinline__ int frame_nth_bit(unsigned long long w, int r) {
-  int base = 0;
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    const unsigned long long lo = w & ((1ull << s) - 1ull);
-    const int c = __popcll(lo);
-    if (r >= c) { r -= c; w >>= s; base += s; } else { w = lo; }
-  }
-  return base;
 }
 
 struct FrameBatch {

@@ -18,4 +18,12 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
   return c;
 }
 
+// a standard normal pair from two random words (Box-Muller, fp32): u1 in (0, 1], u2 in [0, 1) -- the datasets' draws (batch.hip,
+// frame_store.hip)
+__device__ __forceinline__ float2 batch_normal2(uint32_t r1, uint32_t r2) {
+  const float u1 = (float)((r1 >> 8) + 1u) * 0x1p-24f, u2 = (float)(r2 >> 8) * 0x1p-24f;
+  const float rad = sqrtf(-2.0f * logf(u1)), ang = 6.283185307179586f * u2;
+  return make_float2(rad * cosf(ang), rad * sinf(ang));
+}
+
 }  // namespace pvcnn

@@ -7,6 +7,7 @@ files (it points to frustum-pointnets' prepare_data.py), so nothing in it goes f
     frame_batch           one frame -> the batch one iteration of the rgb-detection loader yields, with no device-to-host copy
     detect_frame          frame_batch -> model -> `kitti.frustum_box_predictions`: an (M, 8) table of 3-D boxes
     kitti_label_lines     the table -> the lines evaluate/kitti/frustum/eval.py:254-256 writes (host only)
+    random_shift_box2d    the original's training-time perturbation of 2-D boxes (host only; per sample on the device: frame_store.py)
 
 The definition (projection, image and box tests, the label, the rotation; include/pvcnn_hip.h, "KITTI frames") is fp64 with one
 rounding per operation; tests/frames_truth.py restates it in numpy and the kernels are held to it bit for bit.  Everything that needs a
@@ -25,8 +26,8 @@ import torch
 from . import _lib
 from .modules.functional.backend import _run
 
-__all__ = ['Calibration', 'FrameFrustums', 'read_scan', 'frustum_angle', 'box_corners', 'box_table', 'project_scan', 'extract_frustums',
-           'frame_batch', 'detect_frame', 'kitti_label_lines', 'copies_made', 'BOX_COLUMNS']
+__all__ = ['Calibration', 'FrameFrustums', 'read_scan', 'frustum_angle', 'random_shift_box2d', 'box_corners', 'box_table', 'project_scan',
+           'extract_frustums', 'frame_batch', 'detect_frame', 'kitti_label_lines', 'copies_made', 'BOX_COLUMNS']
 
 BOX_COLUMNS = 18                     # PVCNN_FRAME_BOX_COLUMNS
 MAX_BOXES = 4096                     # PVCNN_FRAME_MAX_BOXES
@@ -107,6 +108,26 @@ def frustum_angle(calib, boxes_2d):
     cu = (boxes_2d[:, 0] + boxes_2d[:, 2]) / 2
     x = ((cu - P[0, 2]) * 20) / P[0, 0] + P[0, 3] / (-P[0, 0])
     return -np.arctan2(np.full_like(x, 20.0), x)
+
+
+def random_shift_box2d(boxes_2d, draws, shift_ratio=0.1):
+    """(M, 4) fp64: the original's training-time perturbation of 2-D boxes (xmin, ymin, xmax, ymax) -- the centre shifted by up to
+    shift_ratio of the box's size, width and height rescaled by 1 -+ shift_ratio -- for `draws` (M, 4) uniforms in [0, 1), in the
+    original's order: centre x, centre y, height, width.  The definition is include/pvcnn_hip.h's ("KITTI frame store"), elementwise
+    fp64; the rows of `DeviceKittiFrames`' parity `params` are built with it, and with `extract_frustums` on its result the original's
+    frozen `augmentX` copies can be made.  shift_ratio == 0 returns the boxes as they are."""
+    boxes = np.asarray(boxes_2d, dtype=np.float64).reshape(-1, 4)
+    u = np.asarray(draws, dtype=np.float64).reshape(-1, 4)
+    if u.shape[0] != boxes.shape[0]:
+        raise ValueError('four draws per box expected')
+    r = float(shift_ratio)
+    if r == 0.0:
+        return boxes.copy()
+    xmin, ymin, xmax, ymax = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
+    w, h, cx, cy = xmax - xmin, ymax - ymin, (xmin + xmax) / 2, (ymin + ymax) / 2
+    cx2, cy2 = cx + (w * r) * (u[:, 0] * 2 - 1), cy + (h * r) * (u[:, 1] * 2 - 1)
+    h2, w2 = h * ((1 + (u[:, 2] * 2) * r) - r), w * ((1 + (u[:, 3] * 2) * r) - r)
+    return np.stack([cx2 - w2 / 2, cy2 - h2 / 2, cx2 + w2 / 2, cy2 + h2 / 2], axis=1)
 
 
 def box_corners(boxes_3d):
