@@ -181,14 +181,30 @@ PVCNN_API int pvcnn_gather_bwd(const float *grad_y, const int32_t *indices, int 
 PVCNN_API int pvcnn_fps(const float *coords, int B, int N, int M, float *distances, int32_t *indices,
               void *stream);
 
+/* ---- Device draws (csrc/philox.h; tests/draws_truth.py) ---------------------------------------------------------------------
+ * The one random stream of the entry points that draw on the device.
+ * `seed`: two int64 words in DEVICE memory (no host round trip; a replayed graph reads fresh words).  The stream is Philox4x32-10
+ * with key (lo32 seed[0], hi32 seed[0]) and counter (a, b, lo32 seed[1], use): a, b are the use's own -- the point or list position
+ * (0 for a per-sample draw) and the sample -- and `use` names who draws, so that one pair of words may key every stage of a loader:
+ *    0  the picks of pvcnn_batch_*, pvcnn_frame_batch, pvcnn_frame_store_batch; pvcnn_mask_select's selection keys
+ *    1  pvcnn_batch_shapenet's jitter; pvcnn_mask_select's shuffle keys
+ *    2  the flip and shift of pvcnn_batch_frustum and pvcnn_frame_store_batch
+ *    3  pvcnn_frame_store_batch's box perturbation
+ *   16 .. 19  pvcnn_augment_draw's per-cloud draws     20  pvcnn_augment_apply's jitter     21  pvcnn_augment_apply's keep
+ * A pick of [0, n) is mulhi(word x, n); n distinct of k in random order are the low halves of the n smallest words x << 32 | a;
+ * a flip is bit 31 of word x; uniforms are word * 2^-32 in [0, 1) or (word + 0.5) * 2^-32 in (0, 1) in fp64, (word >> 8) * 2^-24 in
+ * fp32; normals are Box-Muller pairs of two words in the precision stated.  pvcnn_room_fill keys the same generator with seed[0] but
+ * lays out its own counter (a, b, lo32 seed[1] ^ use, hi32 seed[1]).
+ */
+
 /* ---- foreground selection of logits_mask (Frustum-PVCNN) --------------------------------------------------------
  * replaces the per-cloud Python loop of modules/functional/sampling.py:69-82 (nonzero() sync + numpy draws per cloud).
  * mask (B,N) bytes (non-zero = foreground) -> selected (B,M) int32 point ids:
  *   k = foreground count; k >= M: M distinct foreground points in random order; 0 < k < M: every one M/k times plus M%k
  *   distinct extra ones, shuffled; k == 0: all 0 -- the reference's three cases.
  * Randomness: `choices` (B,M) int32 = positions into the ascending foreground list, supplied by the caller (PARITY MODE:
- * with numpy's own draws the result is bit-identical to the reference), or, when choices is NULL, a Philox4x32-10 stream
- * keyed by `seed` (two int64 in DEVICE memory: key, stream id) -- no host round trip.  count (B) optional: receives k.
+ * with numpy's own draws the result is bit-identical to the reference), or, when choices is NULL, the stream of `seed`
+ * ("Device draws" above) -- no host round trip.  count (B) optional: receives k.
  * N, M <= 8192.
  */
 PVCNN_API int pvcnn_mask_select(const uint8_t *mask, int B, int N, int M, const int32_t *choices, const int64_t *seed,
@@ -203,8 +219,7 @@ PVCNN_API int pvcnn_mask_select(const uint8_t *mask, int B, int N, int M, const 
  * device: a captured launch walks an epoch when the caller adds B to the cursor after it.  Positions, items and parity choices out of
  * range are clamped (no out-of-bounds access); an empty item yields zeros.
  * Randomness as pvcnn_mask_select: `choices` (B, N) int32 rows within the item (PARITY MODE, with the other draws of the dataset
- * kind; bit-identical to the reference for numpy's draws), or, when choices is NULL, a Philox4x32-10 stream keyed by `seed` (two
- * int64 words in device memory: key, stream id).
+ * kind; bit-identical to the reference for numpy's draws), or, when choices is NULL, the stream of `seed` ("Device draws").
  * Outputs are what default_collate makes of the reference's items: features (B, C_out, N) fp32, targets (B, N) int64, ...
  */
 /* LDS the S3DIS launch takes in device mode for N samples from items of at most max_n rows (0: no selection without replacement). */
@@ -248,10 +263,9 @@ PVCNN_API int pvcnn_batch_frustum_rgb(const float *rows, const int64_t *offsets,
  * an axis, a rotation perturbation, axis flips, scale, translation, clipped Gaussian jitter, PointNet++'s random point dropout -- as
  * two launches that never allocate.  Every pointer is device memory except `layout`.
  *
- * pvcnn_augment_draw: params (B, PVCNN_AUGMENT_PARAMS = 24) fp64, one row per cloud, from a Philox4x32-10 stream keyed by `seed` (two
- * int64 words in device memory: key, stream id -- the convention of pvcnn_batch_*; the counters differ, so one pair of words may key
- * an assembly and its augmentation).  Row: [0:9] the matrix Rp row-major, [9] scale s, [10:13] translation t, [13] dropout ratio,
- * [14:18] the raw angles theta, a, b, c, [18:21] the three flip uniforms, [21:24] zeros.
+ * pvcnn_augment_draw: params (B, PVCNN_AUGMENT_PARAMS = 24) fp64, one row per cloud, from the stream of `seed` ("Device draws": one
+ * pair of words may key an assembly and its augmentation).  Row: [0:9] the matrix Rp row-major, [9] scale s, [10:13] translation t,
+ * [13] dropout ratio, [14:18] the raw angles theta, a, b, c, [18:21] the three flip uniforms, [21:24] zeros.
  *   theta ~ U(-rot_max, rot_max) about `axis` (0: x, 1: y, 2: z);  a, b, c = clip(perturb_sigma z, +-perturb_clip), z standard normal;
  *   axis k is flipped when u_k < flip_k;  s ~ U(scale_lo, scale_hi);  t ~ U(-translate_max, translate_max)^3;  ratio = u drop_max.
  *   Rp = Rx(a) Ry(b) Rz(c) R_axis(theta) diag(+-1), right-handed rotations, composed in fp64.
@@ -850,8 +864,9 @@ PVCNN_API int pvcnn_frustum_predictions(const float *center, const float *headin
  * cells that draw from more than 2048 copies (they take the workgroup-per-cell path)].
  * block_tables (5, num_blocks) int32: points, cells, resampled entries, first entry, first window of every merged block.
  * workspace: pvcnn_room_workspace_bytes(n, num_blocks) bytes, 8-byte aligned, for every call that takes one.
- * seed: two int64 words in device memory (the Philox key of the pass).  All fp64 arithmetic is the reference's, one rounding per
- * operation; minima and counts use integer atomics only: two runs with the same seed are bit-identical. */
+ * seed: two int64 words in device memory (the key and counter words of the pass: "Device draws").  All fp64 arithmetic is the
+ * reference's, one rounding per operation; minima and counts use integer atomics only: two runs with the same seed are
+ * bit-identical. */
 PVCNN_API size_t pvcnn_room_workspace_bytes(long long n, long long num_blocks);
 PVCNN_API int pvcnn_room_extent(const double *xyzrgb, long long n, double *extent, void *workspace, size_t workspace_bytes, void *stream);
 /* point_block (n): dense block key bx * gy + by; block_count, block_target (merge map, step 3), block_rank (the reference's block
@@ -1042,7 +1057,7 @@ PVCNN_API int pvcnn_dml_pair_bwd(const float *a, long long a_bstride, const floa
  *   point index, for w < W; offsets (W + 1) int64 from the caller (offsets[w + 1] - offsets[w] = the box's count), R = all rows of
  *   out_rows: nothing is written beyond an item's own range or R.
  * pvcnn_frame_batch: for m < M with k = counts[m][0] selected points, position p of num_points takes choices[m][p] clamped to [0, k)
- *   (parity mode) or mulhi(Philox4x32-10(counter (p, m, lo32 seed[1], 0), key seed[0]).x, k), as pvcnn_batch_* draw; the point at that
+ *   (parity mode) or the pick of [0, k) at (p, m) of the stream of `seed` ("Device draws"), as pvcnn_batch_* draw; the point at that
  *   position (ascending point index) is found through the tile prefix; with `rotate`, x' = fp32(x c + z (-s)), z' = fp32(x s + z c) in
  *   fp64 from the fp32 row (c, s = columns 13, 14).  features (Bmax, 4, num_points), one_hot_vectors (Bmax, K), rotation_angle (Bmax)
  *   fp32, rgb_score (Bmax) fp64, valid (Bmax) bytes.  A box with k < max(min_points, 1) or ymax - ymin < min_box_height, and every row
@@ -1095,22 +1110,22 @@ PVCNN_API int pvcnn_frame_rotate_rows(float *rows, long long R, const long long 
  * the box-frame test of pvcnn_frame_count on the stored fp32 row.  The perturbed box is used iff ymax' - ymin' >= min_box_height and it
  * selects a positive point (used = 1); otherwise the item's stored box with the host's angle, cos and sin (used = 0).
  * Of the k selected points of the box used, position p of N takes choices[b][p] clamped to [0, k) or
- * mulhi(Philox4x32-10(counter (p, b, lo32 seed[1], 0), key seed[0]).x, k), as pvcnn_frame_batch; k == 0 yields zeros.
+ * the pick of [0, k) at (p, b) of the stream of `seed` ("Device draws"), as pvcnn_frame_batch; k == 0 yields zeros.
  * mask_logits = the box-frame test of the picked row.  With frustum_rotate: the row as pvcnn_frame_batch rotates it
  * (x' = fp32(x c + z (-s)), z' = fp32(x s + z c)), the centre cx' = cx c + cz (-s), cz' = cx s + cz c, heading = ry - rotation_angle
  * (c, s, rotation_angle of the box used); without it, rows, centre and heading = ry stay.  dist = sqrt(c0 c0 + c1 c1) of that centre
  * (the reference's expression as written); heading bin and residual = pvcnn_amd.data.angle_to_bin_id of heading, or of pi - heading
  * when flipped (% is numpy's: fmod, plus the divisor when the remainder is non-zero and negative); flip and shift are those of
- * pvcnn_batch_frustum, the same draws (counter (0, b, stream, 2)) and the same arithmetic.
+ * pvcnn_batch_frustum, the same draws (use 2 at (0, b)) and the same arithmetic.
  *
  * PARITY MODE (`choices` given): `params` (B, PVCNN_FRAME_STORE_PARAMS) fp64 rows [0..3] u0..u3, [4..7] the perturbed box,
  * [8] rotation_angle', [9, 10] its cos, sin, [11] zero -- required when shift_ratio != 0; the box and the angle are TAKEN from the row
  * (no trigonometric function runs on the device); `flip` / `shift` (B) fp64 as pvcnn_batch_frustum.  params, flip or shift without
- * choices are refused.  DEVICE MODE: u_j = word j of Philox4x32-10(counter (0, b, lo32 seed[1], 3), key seed[0]) times 2^-32 -- counter
- * word 3 = 3 is used by no other draw of the input side (0: choices, 1: ShapeNet's jitter, 2: flip and shift); cos and sin of
- * rotation_angle' are the device's fp64 library functions.  Optional outputs in both modes: params_out (B, 12) the rows used, `used`
- * (B) int32, choices_out (B, N) int32, flip_out (B) fp64 (1 / 0), shift_out (B) fp64 (the normal draw) -- fed back in parity mode
- * they reproduce the batch bit for bit.  Outputs as pvcnn_batch_frustum.  One launch; never allocates, synchronises or uses an atomic. */
+ * choices are refused.  DEVICE MODE: u_j = word j of use 3 at (0, b) of the stream of `seed` ("Device draws") times 2^-32; cos and
+ * sin of rotation_angle' are the device's fp64 library functions.  Optional outputs in both modes: params_out (B, 12) the rows used,
+ * `used` (B) int32, choices_out (B, N) int32, flip_out (B) fp64 (1 / 0), shift_out (B) fp64 (the normal draw) -- fed back in parity
+ * mode they reproduce the batch bit for bit.  Outputs as pvcnn_batch_frustum.  One launch; never allocates, synchronises or uses an
+ * atomic. */
 #define PVCNN_FRAME_STORE_PARAMS 12
 #define PVCNN_FRAME_STORE_ITEM_COLUMNS 24
 #define PVCNN_FRAME_STORE_MAX_POINTS 131072

@@ -192,8 +192,7 @@ class Augment:
 
     def draw(self, batch_size, seed, out=None):
         """params (B, 24) fp64 on seed's device from the Philox stream of `seed` (two int64 words on the device): one launch."""
-        if not seed.is_cuda or seed.dtype != torch.int64 or seed.numel() < 2 or not seed.is_contiguous():
-            raise ValueError('seed = two int64 words on the device')
+        _seam.check_seed(seed)
         if out is None:
             out = torch.empty((int(batch_size), PARAMS), dtype=torch.float64, device=seed.device)
         elif tuple(out.shape) != (int(batch_size), PARAMS) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != seed.device:
@@ -240,7 +239,7 @@ class Augment:
             seed = None
         else:
             if seed is None:
-                seed = torch.randint(0, 2 ** 62, (2,), device=x.device, dtype=torch.int64)    # device generator: no sync
+                seed = _seam.fresh_seed(x.device)
             params = self.draw(b, seed, params_out)
         jitter_out = keep_out = None
         if return_draws:

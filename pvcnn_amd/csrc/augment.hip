@@ -21,9 +21,9 @@
 // reads point 0 (its planes, its jitter draw, its target) instead of its own, so nothing is read back from `dst` and no thread
 // waits for another.  That is also why dst must not overlap src when dropout is on: point 0 would be overwritten while others read it.
 //
-// RANDOMNESS as batch.hip: the caller's draws (PARITY MODE) or a Philox4x32-10 stream keyed by two int64 words in device memory.  The
-// counter's last word separates the uses of one key: batch.hip takes 0..2, this file 16..21, so a loader may key its assembly and its
-// augmentation with the same two words.
+// RANDOMNESS as batch.hip: the caller's draws (PARITY MODE) or the draw stream of philox.h, keyed by two int64 words in device memory.
+// The counter's last word separates the uses of one key (philox.h's table: the assembly takes 0..3, this file 16..21), so a loader
+// may key its assembly and its augmentation with the same two words.
 #include "common.h"
 #include "philox.h"
 
@@ -36,34 +36,11 @@ constexpr int kAugMaxBlocksX = 1024;           // blocks along N of one pass: be
 // waves, a quarter of the chain each) beats the 16-byte accesses, which pay off once the waves fill the machine either way.
 constexpr long long kAugVecMinPoints = 1ll << 18;
 constexpr int kAugParams = PVCNN_AUGMENT_PARAMS;
-constexpr uint32_t kAugCtrCloud = 16u;         // .. 19: the per-cloud draws
-constexpr uint32_t kAugCtrJitter = 20u, kAugCtrKeep = 21u;
 
 struct AugmentConfig {
   int axis;
   double rot_max, perturb_sigma, perturb_clip, flip_x, flip_y, flip_z, scale_lo, scale_hi, translate_max, drop_max;
 };
-
-__device__ __forceinline__ uint2 aug_key(const int64_t *seed) {
-  return make_uint2((uint32_t)seed[0], (uint32_t)((uint64_t)seed[0] >> 32));
-}
-
-// uniform in (0, 1), fp64, from one word
-__device__ __forceinline__ double aug_uniform(uint32_t r) { return ((double)r + 0.5) * 0x1p-32; }
-
-// a standard normal pair in fp64 from two words (Box-Muller): u1 in (0, 1], u2 in [0, 1)
-__device__ __forceinline__ double2 aug_normal2(uint32_t r1, uint32_t r2) {
-  const double u1 = ((double)r1 + 1.0) * 0x1p-32, u2 = (double)r2 * 0x1p-32;
-  const double rad = sqrt(-2.0 * log(u1)), ang = 6.283185307179586 * u2;
-  return make_double2(rad * cos(ang), rad * sin(ang));
-}
-
-// the per-point normals in fp32 (what `jitter` holds in parity mode and `jitter_out` receives): as batch.hip's
-__device__ __forceinline__ float2 aug_normal2f(uint32_t r1, uint32_t r2) {
-  const float u1 = (float)((r1 >> 8) + 1u) * 0x1p-24f, u2 = (float)(r2 >> 8) * 0x1p-24f;
-  const float rad = sqrtf(-2.0f * logf(u1)), ang = 6.283185307179586f * u2;
-  return make_float2(rad * cosf(ang), rad * sinf(ang));
-}
 
 __device__ __forceinline__ double aug_clip(double v, double c) { return fmin(fmax(v, -c), c); }
 
@@ -95,29 +72,28 @@ __global__ __launch_bounds__(kAugThreads) void augment_draw_kernel(AugmentConfig
                                                                    double *__restrict__ params) {
   const int b = blockIdx.x * kAugThreads + threadIdx.x;
   if (b >= B) return;
-  const uint2 key = aug_key(seed);
-  const uint32_t stream = (uint32_t)seed[1];
-  const uint4 r0 = philox4x32_10(make_uint4(0u, b, stream, kAugCtrCloud), key);          // theta, scale, ratio, -
-  const uint4 r1 = philox4x32_10(make_uint4(0u, b, stream, kAugCtrCloud + 1u), key);     // the perturbation's normals
-  const uint4 r2 = philox4x32_10(make_uint4(0u, b, stream, kAugCtrCloud + 2u), key);     // flips, -
-  const uint4 r3 = philox4x32_10(make_uint4(0u, b, stream, kAugCtrCloud + 3u), key);     // translation, -
+  const DrawStream d = draw_stream(seed);
+  const uint4 r0 = draw_words(d, 0u, b, kDrawAugCloud);          // theta, scale, ratio, -
+  const uint4 r1 = draw_words(d, 0u, b, kDrawAugCloud + 1u);     // the perturbation's normals
+  const uint4 r2 = draw_words(d, 0u, b, kDrawAugCloud + 2u);     // flips, -
+  const uint4 r3 = draw_words(d, 0u, b, kDrawAugCloud + 3u);     // translation, -
   // a range that is off leaves its draw at exactly 0 (or 1): no -0.0, no rounding
-  const double theta = g.rot_max > 0.0 ? g.rot_max * (2.0 * aug_uniform(r0.x) - 1.0) : 0.0;
+  const double theta = g.rot_max > 0.0 ? g.rot_max * (2.0 * open_f64(r0.x) - 1.0) : 0.0;
   double pa = 0.0, pb = 0.0, pc = 0.0;
   if (g.perturb_sigma > 0.0) {
-    const double2 za = aug_normal2(r1.x, r1.y), zb = aug_normal2(r1.z, r1.w);
+    const double2 za = normal2_f64(r1.x, r1.y), zb = normal2_f64(r1.z, r1.w);
     pa = aug_clip(g.perturb_sigma * za.x, g.perturb_clip);
     pb = aug_clip(g.perturb_sigma * za.y, g.perturb_clip);
     pc = aug_clip(g.perturb_sigma * zb.x, g.perturb_clip);
   }
-  const double uf[3] = {aug_uniform(r2.x), aug_uniform(r2.y), aug_uniform(r2.z)};
+  const double uf[3] = {open_f64(r2.x), open_f64(r2.y), open_f64(r2.z)};
   const bool flip[3] = {uf[0] < g.flip_x, uf[1] < g.flip_y, uf[2] < g.flip_z};
-  const double scale = g.scale_lo + (g.scale_hi - g.scale_lo) * aug_uniform(r0.y);
+  const double scale = g.scale_lo + (g.scale_hi - g.scale_lo) * open_f64(r0.y);
   const uint32_t rt[3] = {r3.x, r3.y, r3.z};
   double t[3];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) t[k] = g.translate_max > 0.0 ? g.translate_max * (2.0 * aug_uniform(rt[k]) - 1.0) : 0.0;
-  const double ratio = aug_uniform(r0.z) * g.drop_max;
+  for (int k = 0; k < 3; ++k) t[k] = g.translate_max > 0.0 ? g.translate_max * (2.0 * open_f64(rt[k]) - 1.0) : 0.0;
+  const double ratio = open_f64(r0.z) * g.drop_max;
   // Rp = Rx(a) Ry(b) Rz(c) R_axis(theta) diag(+-1)
   Mat3 m = aug_matmul(aug_matmul(aug_rotation(0, pa), aug_rotation(1, pb)), aug_rotation(2, pc));
   m = aug_matmul(m, aug_rotation(g.axis, theta));
@@ -183,9 +159,7 @@ template <int V>
 __global__ __launch_bounds__(kAugThreads) void augment_apply_kernel(AugmentApply a) {
   const int N = a.N, C = a.C, groups = N / V;
   const bool draw_jitter = a.jitter_on && !a.jitter, draw_keep = a.drop_on && !a.keep;
-  uint2 key = make_uint2(0u, 0u);
-  uint32_t stream = 0u;
-  if (draw_jitter || draw_keep) { key = aug_key(a.seed); stream = (uint32_t)a.seed[1]; }
+  const DrawStream d = draw_stream(draw_jitter || draw_keep ? a.seed : nullptr);
   for (int b = blockIdx.y; b < a.B; b += gridDim.y) {
     const double *prm = a.params + (size_t)b * kAugParams;
     double R[9], t[3];
@@ -208,7 +182,7 @@ __global__ __launch_bounds__(kAugThreads) void augment_apply_kernel(AugmentApply
           u = aug_load<V>(a.keep + (size_t)b * N + n0);
         } else {
 #pragma unroll
-          for (int j = 0; j < V; ++j) u.v[j] = (float)(philox4x32_10(make_uint4(n0 + j, b, stream, kAugCtrKeep), key).x >> 8) * 0x1p-24f;
+          for (int j = 0; j < V; ++j) u.v[j] = unit_f32(draw_words(d, n0 + j, b, kDrawAugKeep).x);
         }
         if (a.keep_out) aug_store<V>(a.keep_out + (size_t)b * N + n0, u);
 #pragma unroll
@@ -231,8 +205,8 @@ __global__ __launch_bounds__(kAugThreads) void augment_apply_kernel(AugmentApply
         } else {
 #pragma unroll
           for (int j = 0; j < V; ++j) {
-            const uint4 r4 = philox4x32_10(make_uint4(n0 + j, b, stream, kAugCtrJitter), key);
-            const float2 za = aug_normal2f(r4.x, r4.y), zb = aug_normal2f(r4.z, r4.w);
+            const uint4 r4 = draw_words(d, n0 + j, b, kDrawAugJitter);
+            const float2 za = normal2_f32(r4.x, r4.y), zb = normal2_f32(r4.z, r4.w);
             z[0].v[j] = za.x; z[1].v[j] = za.y; z[2].v[j] = zb.x;
           }
         }
@@ -246,8 +220,8 @@ __global__ __launch_bounds__(kAugThreads) void augment_apply_kernel(AugmentApply
 #pragma unroll
             for (int k = 0; k < 3; ++k) z0[k] = a.jitter[((size_t)b * 3 + k) * N];
           } else {
-            const uint4 r4 = philox4x32_10(make_uint4(0u, b, stream, kAugCtrJitter), key);
-            const float2 za = aug_normal2f(r4.x, r4.y), zb = aug_normal2f(r4.z, r4.w);
+            const uint4 r4 = draw_words(d, 0u, b, kDrawAugJitter);
+            const float2 za = normal2_f32(r4.x, r4.y), zb = normal2_f32(r4.z, r4.w);
             z0[0] = za.x; z0[1] = za.y; z0[2] = zb.x;
           }
 #pragma unroll

@@ -24,6 +24,7 @@
 // Positions and items outside [0, order_len) / [0, W) and parity choices outside [0, n) are clamped: the kernels never read outside the
 // store, whatever the device words hold.  An empty item yields zeros.
 #include "common.h"
+#include "frame_tiles.h"
 #include "philox.h"
 
 namespace pvcnn {
@@ -42,8 +43,6 @@ struct BatchStore {
   int label_bytes, N;
 };
 
-__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __device__ __forceinline__ long long batch_label(const BatchStore &s, long long row) {
   switch (s.label_bytes) {
     case 1: return static_cast<const uint8_t *>(s.labels)[row];
@@ -55,23 +54,18 @@ __device__ __forceinline__ long long batch_label(const BatchStore &s, long long 
 
 // the item of sample b: its index, first row and row count (workgroup-uniform)
 __device__ __forceinline__ long long batch_item(const BatchStore &s, int b, long long &start, int &n) {
-  const long long pos = clampll((s.cursor ? s.cursor[0] : 0ll) + b, 0ll, s.order_len - 1);
-  const long long item = clampll(s.order[pos], 0ll, s.W - 1);
+  const long long item = sample_item(s.order, s.cursor, s.order_len, s.W, b);
   start = s.offsets[item];
   n = (int)clampll(s.offsets[item + 1] - start, 0ll, 0x7fffffffll);
   return item;
 }
 
-__device__ __forceinline__ uint2 batch_key(const BatchStore &s) {
-  return make_uint2((uint32_t)s.seed[0], (uint32_t)((uint64_t)s.seed[0] >> 32));
-}
-
 // words[0 .. N) <- N distinct of n in random order (low halves); npad = n rounded up to a power of two <= kBatchMaxSort
-__device__ __forceinline__ void batch_sort_select(unsigned long long *words, int n, int b, uint32_t stream, uint2 key) {
+__device__ __forceinline__ void batch_sort_select(unsigned long long *words, int n, int b, const DrawStream &d) {
   int npad = 1;
   while (npad < n) npad <<= 1;
   for (int i = threadIdx.x; i < npad; i += kBatchThreads)
-    words[i] = i < n ? ((unsigned long long)philox4x32_10(make_uint4(i, b, stream, 0u), key).x << 32) | (unsigned)i : ~0ull;
+    words[i] = i < n ? draw_sort_word(d, i, b) : ~0ull;
   __syncthreads();
   for (int k = 2; k <= npad; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
@@ -87,10 +81,10 @@ __device__ __forceinline__ void batch_sort_select(unsigned long long *words, int
 
 // the row (within its item) of output point p
 __device__ __forceinline__ int batch_pick(const BatchStore &s, const unsigned long long *words, bool sorted, int b, int p, int n,
-                                          uint32_t stream, uint2 key) {
+                                          const DrawStream &d) {
   if (s.choices) return min(max(s.choices[(size_t)b * s.N + p], 0), n - 1);
   if (sorted) return (int)(uint32_t)words[p];
-  return (int)mulhi32(philox4x32_10(make_uint4(p, b, stream, 0u), key).x, (uint32_t)n);
+  return (int)draw_index(d, p, b, n);
 }
 
 // ---- S3DIS: features (B, c_out, N) = the first c_out of 9 stored channels, targets (B, N) ----
@@ -110,17 +104,11 @@ __global__ __launch_bounds__(kBatchThreads) void batch_s3dis_kernel(BatchStore s
     }
     return;
   }
-  uint2 key = make_uint2(0u, 0u);
-  uint32_t stream = 0u;
-  bool sorted = false;
-  if (!s.choices) {
-    key = batch_key(s);
-    stream = (uint32_t)s.seed[1];
-    sorted = n >= N && n <= sort_cap;          // np.random.choice(n, N, replace=n < N)
-    if (sorted) batch_sort_select(batch_words, n, b, stream, key);
-  }
+  const DrawStream d = draw_stream(s.choices ? nullptr : s.seed);
+  const bool sorted = !s.choices && n >= N && n <= sort_cap;        // np.random.choice(n, N, replace=n < N)
+  if (sorted) batch_sort_select(batch_words, n, b, d);
   for (int p = threadIdx.x; p < N; p += kBatchThreads) {
-    const long long row = start + batch_pick(s, batch_words, sorted, b, p, n, stream, key);
+    const long long row = start + batch_pick(s, batch_words, sorted, b, p, n, d);
     const float *r = s.rows + row * 9;
     float v[9];
 #pragma unroll
@@ -144,14 +132,12 @@ __global__ __launch_bounds__(kBatchThreads) void batch_shapenet_kernel(BatchStor
   const int shape = shape_ids[item];
   float *f = features + (size_t)b * c_out * N;
   int64_t *tg = targets + (size_t)b * N;
-  uint2 key = make_uint2(0u, 0u);
-  uint32_t stream = 0u;
-  if (!s.choices) { key = batch_key(s); stream = (uint32_t)s.seed[1]; }
+  const DrawStream d = draw_stream(s.choices ? nullptr : s.seed);
   for (int p = threadIdx.x; p < N; p += kBatchThreads) {
     float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     long long label = 0;
     if (n > 0) {
-      const long long row = start + batch_pick(s, nullptr, false, b, p, n, stream, key);
+      const long long row = start + batch_pick(s, nullptr, false, b, p, n, d);
       const float *r = s.rows + row * 6;
 #pragma unroll
       for (int c = 0; c < 6; ++c) v[c] = r[c];
@@ -164,8 +150,8 @@ __global__ __launch_bounds__(kBatchThreads) void batch_shapenet_kernel(BatchStor
             v[c] = (float)fmin(fmax(0.01 * z, -0.05), 0.05) + v[c];
           }
         } else {
-          const uint4 r4 = philox4x32_10(make_uint4(p, b, stream, 1u), key);
-          const float2 za = batch_normal2(r4.x, r4.y), zb = batch_normal2(r4.z, r4.w);
+          const uint4 r4 = draw_words(d, p, b, kDrawJitter);
+          const float2 za = normal2_f32(r4.x, r4.y), zb = normal2_f32(r4.z, r4.w);
           v[0] = fminf(fmaxf(0.01f * za.x, -0.05f), 0.05f) + v[0];
           v[1] = fminf(fmaxf(0.01f * za.y, -0.05f), 0.05f) + v[1];
           v[2] = fminf(fmaxf(0.01f * zb.x, -0.05f), 0.05f) + v[2];
@@ -204,19 +190,15 @@ __global__ __launch_bounds__(kBatchThreads) void batch_frustum_kernel(BatchStore
   long long start;
   int n;
   const long long item = batch_item(s, b, start, n);
-  uint2 key = make_uint2(0u, 0u);
-  uint32_t stream = 0u;
-  if (!s.choices) { key = batch_key(s); stream = (uint32_t)s.seed[1]; }
+  const DrawStream d = draw_stream(s.choices ? nullptr : s.seed);
   bool flipped = false;
   double shift = 0.0;
   if (!a.rgb) {
-    uint4 r4 = make_uint4(0u, 0u, 0u, 0u);
-    if (!s.choices && (a.random_flip || a.random_shift)) r4 = philox4x32_10(make_uint4(0u, b, stream, 2u), key);
-    if (a.random_flip) flipped = s.choices ? a.flip[b] > 0.5 : (r4.x >> 31) != 0u;     // np.random.random() > 0.5
+    const FlipShift fs = draw_flip_shift(d, b, a.random_flip, a.random_shift, s.choices != nullptr, a.flip, a.shift);
+    flipped = fs.flipped;
     if (a.random_shift) {                      // np.clip(randn() * dist * 0.05, dist * 0.8, dist * 1.2): the reference's expression as written
       const double dist = a.item_f64[item * 4 + 3];
-      const double z = s.choices ? a.shift[b] : (double)batch_normal2(r4.y, r4.z).x;
-      shift = fmin(fmax(z * dist * 0.05, dist * 0.8), dist * 1.2);
+      shift = fmin(fmax(fs.z * dist * 0.05, dist * 0.8), dist * 1.2);
     }
   }
   float *f = a.features + (size_t)b * 4 * N;
@@ -224,7 +206,7 @@ __global__ __launch_bounds__(kBatchThreads) void batch_frustum_kernel(BatchStore
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     long long label = 0;
     if (n > 0) {
-      const long long row = start + batch_pick(s, nullptr, false, b, p, n, stream, key);
+      const long long row = start + batch_pick(s, nullptr, false, b, p, n, d);
       const float *r = s.rows + row * 4;
 #pragma unroll
       for (int c = 0; c < 4; ++c) v[c] = r[c];
@@ -232,8 +214,7 @@ __global__ __launch_bounds__(kBatchThreads) void batch_frustum_kernel(BatchStore
       if (flipped) v[0] = -v[0];
       if (a.random_shift && !a.rgb) v[2] = (float)((double)v[2] + shift);            // fp64 sum, rounded once
     }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) f[(size_t)c * N + p] = v[c];
+    store_planes4(f, N, p, make_float4(v[0], v[1], v[2], v[3]));
     if (!a.rgb) a.mask_logits[(size_t)b * N + p] = label;
   }
   // the per-item words: a few lanes of the first wave

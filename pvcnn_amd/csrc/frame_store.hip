@@ -30,7 +30,6 @@ constexpr int kFsWaves = kFsThreads / kWave;
 constexpr int kFsItemCols = PVCNN_FRAME_STORE_ITEM_COLUMNS;
 constexpr int kFsParams = PVCNN_FRAME_STORE_PARAMS;
 constexpr long long kFsMaxPoints = PVCNN_FRAME_STORE_MAX_POINTS;
-constexpr uint32_t kFsCtrBox = 3u;             // Philox counter word 3 of the box draw (0: choices, 1: ShapeNet's jitter, 2: flip and shift)
 
 struct FrameStoreBatch {
   const float4 *rows;                          // (R) fp32 rows of the in-image points of every frame
@@ -50,8 +49,6 @@ struct FrameStoreBatch {
   double *params_out, *flip_out, *shift_out;
   int32_t *used, *choices_out;
 };
-
-__device__ __forceinline__ long long fs_clamp(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // numpy's % on doubles: fmod, then the divisor added when the remainder is non-zero and of the other sign (m > 0 here)
 __device__ __forceinline__ double fs_floor_mod(double x, double m) {
@@ -81,22 +78,16 @@ __global__ __launch_bounds__(kFsThreads) void frame_store_batch_kernel(FrameStor
   int *s_prefix = reinterpret_cast<int *>(fs_lds + 2 * T);           // [2][T + 1]
 
   // the item of this sample and the points of its frame (workgroup-uniform)
-  const long long at = fs_clamp((a.cursor ? a.cursor[0] : 0ll) + b, 0ll, a.order_len - 1);
-  const long long item = fs_clamp(a.order[at], 0ll, a.W - 1);
+  const long long item = sample_item(a.order, a.cursor, a.order_len, a.W, b);
   const double *it = a.item_f64 + item * kFsItemCols;
-  const long long frame = fs_clamp(a.item_i64[item * 3], 0ll, a.F - 1);
-  const long long start = fs_clamp(a.frame_offsets[frame], 0ll, a.R);
+  const long long frame = clampll(a.item_i64[item * 3], 0ll, a.F - 1);
+  const long long start = clampll(a.frame_offsets[frame], 0ll, a.R);
   long long room = a.R - start;
   if (room > T * kFrameTile) room = T * kFrameTile;
-  const long long n = fs_clamp(a.frame_offsets[frame + 1] - start, 0ll, room);
+  const long long n = clampll(a.frame_offsets[frame + 1] - start, 0ll, room);
   const long long tiles = (n + kFrameTile - 1) / kFrameTile;
   const bool parity = a.choices != nullptr, perturb = a.shift_ratio != 0.0;
-  uint2 key = make_uint2(0u, 0u);
-  uint32_t stream = 0u;
-  if (!parity) {
-    key = make_uint2((uint32_t)a.seed[0], (uint32_t)((uint64_t)a.seed[0] >> 32));
-    stream = (uint32_t)a.seed[1];
-  }
+  const DrawStream d = draw_stream(parity ? nullptr : a.seed);
 
   // (a) the perturbed box and its frustum angle
   if (t == 0) {
@@ -107,8 +98,8 @@ __global__ __launch_bounds__(kFsThreads) void frame_store_batch_kernel(FrameStor
       for (int j = 0; j < 4; ++j) { u[j] = p[j]; bx[j] = p[4 + j]; }
       ang = p[8]; c = p[9]; s = p[10];
     } else if (perturb) {
-      const uint4 r4 = philox4x32_10(make_uint4(0u, (uint32_t)b, stream, kFsCtrBox), key);
-      u[0] = (double)r4.x * 0x1p-32; u[1] = (double)r4.y * 0x1p-32; u[2] = (double)r4.z * 0x1p-32; u[3] = (double)r4.w * 0x1p-32;
+      const uint4 r4 = draw_words(d, 0u, b, kDrawBox);
+      u[0] = unit_f64(r4.x); u[1] = unit_f64(r4.y); u[2] = unit_f64(r4.z); u[3] = unit_f64(r4.w);
       const double r = a.shift_ratio;
       const double w = bx[2] - bx[0], h = bx[3] - bx[1], cx = (bx[0] + bx[2]) / 2.0, cy = (bx[1] + bx[3]) / 2.0;
       const double cx2 = cx + (w * r) * (u[0] * 2.0 - 1.0), cy2 = cy + (h * r) * (u[1] * 2.0 - 1.0);
@@ -146,9 +137,7 @@ __global__ __launch_bounds__(kFsThreads) void frame_store_batch_kernel(FrameStor
     if (live) { p = uvp[i]; r = rp[i]; }
     const bool in_p = live && p.x >= px0 && p.x < px1 && p.y >= py0 && p.y < py1;
     const bool in_u = live && p.x >= ux0 && p.x < ux1 && p.y >= uy0 && p.y < uy1;
-    const double dx = (double)r.x - tx, dy = (double)r.y - ty, dz = (double)r.z - tz;
-    const double xl = cr * dx - sr * dz, zl = sr * dx + cr * dz;
-    const bool inside = fabs(xl) <= bl / 2.0 && fabs(zl) <= bw / 2.0 && dy <= 0.0 && dy >= -bh;
+    const bool inside = inside_box3d((double)r.x - tx, (double)r.y - ty, (double)r.z - tz, bh, bw, bl, cr, sr);
     const unsigned long long mp = __ballot(in_p), mu = __ballot(in_u);
     positives[0] += __popcll(__ballot(in_p && inside));
     positives[1] += __popcll(__ballot(in_u && inside));
@@ -198,21 +187,14 @@ __global__ __launch_bounds__(kFsThreads) void frame_store_batch_kernel(FrameStor
   // the targets that depend on the rotation used and on the flip and shift draws
   double cen[3] = {it[16], it[17], it[18]}, heading = it[15];
   if (a.rotate) {
-    const double x = cen[0], z = cen[2];
-    cen[0] = x * c + z * (-s);
-    cen[2] = x * s + z * c;
+    rotate_y(cen[0], cen[2], c, s);
     heading = heading - ang;
   }
   const double dist = sqrt(cen[0] * cen[0] + cen[1] * cen[1]);
-  bool flipped = false;
-  double shift = 0.0, z_draw = 0.0;
-  uint4 r4 = make_uint4(0u, 0u, 0u, 0u);
-  if (!parity && (a.random_flip || a.random_shift)) r4 = philox4x32_10(make_uint4(0u, (uint32_t)b, stream, 2u), key);
-  if (a.random_flip) flipped = parity ? a.flip[b] > 0.5 : (r4.x >> 31) != 0u;
-  if (a.random_shift) {                        // np.clip(randn() * dist * 0.05, dist * 0.8, dist * 1.2): the reference's expression as written
-    z_draw = parity ? a.shift[b] : (double)batch_normal2(r4.y, r4.z).x;
-    shift = fmin(fmax(z_draw * dist * 0.05, dist * 0.8), dist * 1.2);
-  }
+  const FlipShift fs = draw_flip_shift(d, b, a.random_flip, a.random_shift, parity, a.flip, a.shift);
+  const bool flipped = fs.flipped;
+  // np.clip(randn() * dist * 0.05, dist * 0.8, dist * 1.2): the reference's expression as written
+  const double shift = a.random_shift ? fmin(fmax(fs.z * dist * 0.05, dist * 0.8), dist * 1.2) : 0.0;
   if (t == 0) {
     long long bin;
     float residual;
@@ -223,7 +205,7 @@ __global__ __launch_bounds__(kFsThreads) void frame_store_batch_kernel(FrameStor
     a.class_id[b] = a.item_i64[item * 3 + 2];
     if (a.used) a.used[b] = accept ? 1 : 0;
     if (a.flip_out) a.flip_out[b] = flipped ? 1.0 : 0.0;
-    if (a.shift_out) a.shift_out[b] = z_draw;
+    if (a.shift_out) a.shift_out[b] = fs.z;
   }
   if (t < 3) {
     double v = cen[t];
@@ -241,33 +223,16 @@ __global__ __launch_bounds__(kFsThreads) void frame_store_batch_kernel(FrameStor
     long long label = 0;
     int pos = 0;
     if (k > 0) {
-      if (parity) pos = min(max(a.choices[(size_t)b * N + p], 0), k - 1);
-      else pos = (int)mulhi32(philox4x32_10(make_uint4((uint32_t)p, (uint32_t)b, stream, 0u), key).x, (uint32_t)k);
-      long long lo = 0, hi = tiles - 1;        // the last tile with prefix <= pos holds it (empty tiles share a prefix with the next)
-      while (lo < hi) {
-        const long long mid = (lo + hi + 1) >> 1;
-        if (pf[mid] <= pos) lo = mid; else hi = mid - 1;
-      }
-      const unsigned long long bits = mk[lo];
-      const int r = pos - pf[lo];
-      long long i = lo * kFrameTile + ((r >= 0 && r < (int)__popcll(bits)) ? frame_nth_bit(bits, r) : 0);
+      pos = parity ? min(max(a.choices[(size_t)b * N + p], 0), k - 1) : (int)draw_index(d, p, b, k);
+      long long i = frame_pick(pf, mk, tiles, pos);
       if (i > n - 1) i = n - 1;
       v = rp[i];
-      const double dx = (double)v.x - tx, dy = (double)v.y - ty, dz = (double)v.z - tz;
-      const double xl = cr * dx - sr * dz, zl = sr * dx + cr * dz;
-      label = (fabs(xl) <= bl / 2.0 && fabs(zl) <= bw / 2.0 && dy <= 0.0 && dy >= -bh) ? 1 : 0;
-      if (a.rotate) {                          // fp64 from the fp32 row, rounded once
-        const double x = (double)v.x, z = (double)v.z;
-        v.x = (float)(x * c + z * (-s));
-        v.z = (float)(x * s + z * c);
-      }
+      label = inside_box3d((double)v.x - tx, (double)v.y - ty, (double)v.z - tz, bh, bw, bl, cr, sr) ? 1 : 0;
+      if (a.rotate) rotate_y(v, c, s);
       if (flipped) v.x = -v.x;
       if (a.random_shift) v.z = (float)((double)v.z + shift);
     }
-    f[p] = v.x;
-    f[(size_t)N + p] = v.y;
-    f[(size_t)2 * N + p] = v.z;
-    f[(size_t)3 * N + p] = v.w;
+    store_planes4(f, N, p, v);
     a.mask_logits[(size_t)b * N + p] = label;
     if (a.choices_out) a.choices_out[(size_t)b * N + p] = pos;
   }

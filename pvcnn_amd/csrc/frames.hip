@@ -79,10 +79,7 @@ __global__ __launch_bounds__(kFrameThreads) void frame_masks_kernel(const double
     if (label_mask) {
       bool inside = false;
       if (b[4] != 0.0) {                       // a 3-D box (h, w, l, t, cos ry, sin ry): the box-frame form of the hull test
-        const double h = b[5], w = b[6], l = b[7], c = b[11], s = b[12];
-        const double dx = X - b[8], dy = Y - b[9], dz = Z - b[10];
-        const double xl = c * dx - s * dz, zl = s * dx + c * dz;
-        inside = in_box && fabs(xl) <= l / 2.0 && fabs(zl) <= w / 2.0 && dy <= 0.0 && dy >= -h;
+        inside = in_box && inside_box3d(X - b[8], Y - b[9], Z - b[10], b[5], b[6], b[7], b[11], b[12]);
       }
       const unsigned long long lbits = __ballot(inside);
       if (lane == 0) label_mask[(size_t)m * tiles + tile] = lbits;
@@ -191,35 +188,14 @@ __global__ __launch_bounds__(kFrameThreads) void frame_batch_kernel(FrameBatch a
   const unsigned long long *mk = a.mask + (size_t)m * a.tiles;
   const int *pf = a.prefix + (size_t)m * (a.tiles + 1);
   const double c = b[13], s = b[14];
-  uint2 key = make_uint2(0u, 0u);
-  uint32_t stream = 0u;
-  if (!a.choices) {
-    key = make_uint2((uint32_t)a.seed[0], (uint32_t)((uint64_t)a.seed[0] >> 32));
-    stream = (uint32_t)a.seed[1];
-  }
+  const DrawStream d = draw_stream(a.choices ? nullptr : a.seed);
   for (int p = t; p < N; p += kFrameThreads) {
-    int pos;
-    if (a.choices) pos = min(max(a.choices[(size_t)m * N + p], 0), k - 1);
-    else pos = (int)mulhi32(philox4x32_10(make_uint4(p, m, stream, 0u), key).x, (uint32_t)k);
-    long long lo = 0, hi = a.tiles - 1;        // the last tile with prefix <= pos holds it (empty tiles share a prefix with the next)
-    while (lo < hi) {
-      const long long mid = (lo + hi + 1) >> 1;
-      if (pf[mid] <= pos) lo = mid; else hi = mid - 1;
-    }
-    const unsigned long long bits = mk[lo];
-    const int r = pos - pf[lo];
-    long long i = lo * kFrameTile + ((r >= 0 && r < (int)__popcll(bits)) ? frame_nth_bit(bits, r) : 0);
+    const int pos = a.choices ? min(max(a.choices[(size_t)m * N + p], 0), k - 1) : (int)draw_index(d, p, m, k);
+    long long i = frame_pick(pf, mk, a.tiles, pos);
     if (i > a.cap - 1) i = a.cap - 1;
     float4 v = a.rows[i];
-    if (a.rotate) {                            // fp64 from the fp32 row, rounded once
-      const double x = (double)v.x, z = (double)v.z;
-      v.x = (float)(x * c + z * (-s));
-      v.z = (float)(x * s + z * c);
-    }
-    f[p] = v.x;
-    f[(size_t)N + p] = v.y;
-    f[(size_t)2 * N + p] = v.z;
-    f[(size_t)3 * N + p] = v.w;
+    if (a.rotate) rotate_y(v, c, s);
+    store_planes4(f, N, p, v);
   }
 }
 
@@ -235,11 +211,8 @@ __global__ __launch_bounds__(kFrameThreads) void frame_rotate_rows_kernel(float4
     if (offsets[mid] <= i) lo = mid; else hi = mid - 1;
   }
   if (i < offsets[lo] || i >= offsets[lo + 1]) return;      // a row no item owns stays as it is
-  const double c = cos_sin[2 * lo], s = cos_sin[2 * lo + 1];
   float4 v = rows[i];
-  const double x = (double)v.x, z = (double)v.z;
-  v.x = (float)(x * c + z * (-s));
-  v.z = (float)(x * s + z * c);
+  rotate_y(v, cos_sin[2 * lo], cos_sin[2 * lo + 1]);
   rows[i] = v;
 }
 

@@ -75,9 +75,8 @@ __global__ __launch_bounds__(kSelThreads) void mask_select_kernel(const uint8_t 
     return;
   }
   // ---- 2b. device RNG ----
-  const uint2 key = make_uint2((uint32_t)seed[0], (uint32_t)((uint64_t)seed[0] >> 32));
-  const uint32_t stream = (uint32_t)seed[1];
-  for (int i = tid; i < k; i += kSelThreads) keys[i] = philox4x32_10(make_uint4(i, b, stream, 0u), key).x;
+  const DrawStream d = draw_stream(seed);
+  for (int i = tid; i < k; i += kSelThreads) keys[i] = draw_words(d, i, b, kDrawPick).x;
   __syncthreads();
   if (k >= M) {
     for (int i = tid; i < k; i += kSelThreads) {
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(kSelThreads) void mask_select_kernel(const uint8_t 
     if (r < extra) entry[rep * k + r] = i;                                           // choice(k, M % k, replace=False)
   }
   __syncthreads();
-  for (int s = tid; s < M; s += kSelThreads) keys[s] = philox4x32_10(make_uint4(s, b, stream, 1u), key).x;
+  for (int s = tid; s < M; s += kSelThreads) keys[s] = draw_words(d, s, b, kDrawJitter).x;   // word 1: here the shuffle's keys
   __syncthreads();
   for (int s = tid; s < M; s += kSelThreads) out[rank_of(keys, M, keys[s], s)] = cand[entry[s]];   // shuffle
 }

@@ -349,8 +349,8 @@ struct RoomSeed {
   uint32_t c2, c3;
 };
 __device__ __forceinline__ RoomSeed room_seed(const long long *__restrict__ seed) {
-  const unsigned long long a = (unsigned long long)seed[0], b = (unsigned long long)seed[1];
-  return {make_uint2((uint32_t)a, (uint32_t)(a >> 32)), (uint32_t)b, (uint32_t)(b >> 32)};
+  const DrawStream d = draw_stream(reinterpret_cast<const int64_t *>(seed));           // this file's counter: c2 ^ use, c3
+  return {d.key, d.stream, (uint32_t)((unsigned long long)seed[1] >> 32)};
 }
 __device__ __forceinline__ uint4 room_draw(const RoomSeed &s, uint32_t stream, uint32_t a, uint32_t b) {
   return philox4x32_10(make_uint4(a, b, s.c2 ^ stream, s.c3), s.key);

@@ -138,11 +138,26 @@ class _Store:
         return t
 
     def _seed(self, seed):
-        if seed is None:
-            return torch.randint(0, 2 ** 62, (2,), device=self.device, dtype=torch.int64)      # device generator: no sync
-        if seed.dtype != torch.int64 or seed.numel() < 2:
-            raise ValueError('seed = two int64 words on the device')
-        return seed
+        return _seam.fresh_seed(self.device) if seed is None else _seam.check_seed(seed, self.rows.device)
+
+    def _begin(self, indices, out, order, cursor, batch_size, choices):
+        """The shared opening of every `assemble` -> (backend, order, cursor, B, out (checked, or allocated), choices (B, N) int32)."""
+        be = self._backend()
+        order, cursor, b = self._indices(indices, order, cursor, batch_size)
+        if out is None:
+            out = self.empty_batch(b)
+        else:
+            self._check_out(out, self._describe(b))
+        return be, order, cursor, b, out, self._draw(choices, (b, self.num_points), torch.int32, 'choices')
+
+    @staticmethod
+    def _parity(choices, **draws):
+        """The rule of parity mode: with `choices` every needed draw is present, without it none is.  draws: name -> (tensor, needed)."""
+        names = ' / '.join(f'`{k}`' for k in draws)
+        if choices is None and any(t is not None for t, _ in draws.values()):
+            raise ValueError(f'{names} draws without `choices`: parity mode takes every draw from the caller')
+        if choices is not None and any(needed and t is None for t, needed in draws.values()):
+            raise ValueError(f'parity mode takes every draw from the caller: {names} fp64 are missing')
 
     def _backend(self):
         be = _seam._backend
@@ -252,13 +267,7 @@ class DeviceS3DIS(_Store):
 
     def assemble(self, indices=None, out=None, *, choices=None, jitter=None, flip=None, shift=None, seed=None, order=None, cursor=None,
                  batch_size=None):
-        be = self._backend()
-        order, cursor, b = self._indices(indices, order, cursor, batch_size)
-        if out is None:
-            out = self.empty_batch(b)
-        else:
-            self._check_out(out, self._describe(b))
-        choices = self._draw(choices, (b, self.num_points), torch.int32, 'choices')
+        be, order, cursor, b, out, choices = self._begin(indices, out, order, cursor, batch_size, choices)
         if choices is None and self.max_n >= self.num_points and self.max_n > 8192:
             raise RuntimeError(f'sampling {self.num_points} of up to {self.max_n} points without replacement: the selection is '
                                'resident in LDS and holds at most 8192 points per window')
@@ -344,18 +353,9 @@ class DeviceShapeNet(_Store):
 
     def assemble(self, indices=None, out=None, *, choices=None, jitter=None, flip=None, shift=None, seed=None, order=None, cursor=None,
                  batch_size=None):
-        be = self._backend()
-        order, cursor, b = self._indices(indices, order, cursor, batch_size)
-        if out is None:
-            out = self.empty_batch(b)
-        else:
-            self._check_out(out, self._describe(b))
-        choices = self._draw(choices, (b, self.num_points), torch.int32, 'choices')
+        be, order, cursor, b, out, choices = self._begin(indices, out, order, cursor, batch_size, choices)
         jitter = self._draw(jitter, (b, 3, self.num_points), torch.float64, 'jitter')
-        if choices is not None and self.jitter and jitter is None:
-            raise ValueError('parity mode of a jittering split needs the `jitter` draws (B, 3, N) fp64')
-        if choices is None and jitter is not None:
-            raise ValueError('`jitter` draws without `choices`: parity mode takes every draw from the caller')
+        self._parity(choices, jitter=(jitter, self.jitter))
         be.batch_launch('batch_shapenet', self.rows, self.rows, self.labels, self._label_bytes(), self.offsets, len(self),
                         self.shape_ids, order, order.numel(), cursor, b, self.num_points, int(self.with_normal),
                         self.num_shapes if self.with_one_hot_shape_id else 0, int(self.jitter), choices, jitter,
@@ -473,7 +473,6 @@ class DeviceFrustumKitti(_Store):
         per-item tables come from the frames' small host arrays through the constructor's own code.  With frustum_rotate the packed
         rows are rotated by one launch (csrc/frames.hip) in the elementwise fp64 form x' = x c + z (-s), z' = x s + z c, rounded once:
         within one fp32 ulp of the constructor's BLAS product.  Serves the ground-truth form and the rgb-detection form."""
-        from . import frames as _frames
         frames = [frames] if hasattr(frames, 'rows') else list(frames)
         frames = [f for f in frames if len(f)]
         if not frames:
@@ -520,7 +519,7 @@ class DeviceFrustumKitti(_Store):
         if self.rows.shape[0] != int(offsets[-1]):
             raise ValueError('the frames\' counts do not add up to their rows')
         if self.frustum_rotate:
-            _frames._call('frame_rotate_rows', self.rows, self.rows, self.rows.shape[0], self.offsets, w, torch.from_numpy(cos_sin).to(device))
+            _seam._device_call('frame_rotate_rows', self.rows, self.rows, self.rows.shape[0], self.offsets, w, torch.from_numpy(cos_sin).to(device))
         self._tables = ['rows', 'labels', 'offsets']
         self._upload_item_tables(tables)
         return self
@@ -586,13 +585,7 @@ class DeviceFrustumKitti(_Store):
 
     def assemble(self, indices=None, out=None, *, choices=None, jitter=None, flip=None, shift=None, seed=None, order=None, cursor=None,
                  batch_size=None):
-        be = self._backend()
-        order, cursor, b = self._indices(indices, order, cursor, batch_size)
-        if out is None:
-            out = self.empty_batch(b)
-        else:
-            self._check_out(out, self._describe(b))
-        choices = self._draw(choices, (b, self.num_points), torch.int32, 'choices')
+        be, order, cursor, b, out, choices = self._begin(indices, out, order, cursor, batch_size, choices)
         seed = None if choices is not None else self._seed(seed)
         x, y = out
         if self.rgb_detection:
@@ -601,10 +594,7 @@ class DeviceFrustumKitti(_Store):
                             x['one_hot_vectors'], y['rotation_angle'], y['rgb_score'])
             return out
         flip, shift = self._draw(flip, (b,), torch.float64, 'flip'), self._draw(shift, (b,), torch.float64, 'shift')
-        if choices is not None and ((self.random_flip and flip is None) or (self.random_shift and shift is None)):
-            raise ValueError('parity mode takes every draw from the caller: `flip` (B) / `shift` (B) fp64 are missing')
-        if choices is None and (flip is not None or shift is not None):
-            raise ValueError('`flip` / `shift` draws without `choices`: parity mode takes every draw from the caller')
+        self._parity(choices, flip=(flip, self.random_flip), shift=(shift, self.random_shift))
         be.batch_launch('batch_frustum', self.rows, self.rows, self.labels, self._label_bytes(), self.offsets, len(self), self.item_f64,
                         self.item_f32, self.item_i64, self.num_classes, int(self.random_flip), int(self.random_shift), order,
                         order.numel(), cursor, b, self.num_points, choices, flip, shift, seed, x['features'], x['one_hot_vectors'],
@@ -681,7 +671,7 @@ class DeviceLoader:
         batch of drop_last=False goes through `__iter__` and the step's eager path."""
         out = self.static_batch()
         if seed is None and (choices is None or self.augment is not None):
-            seed = self.seed.random_(0, 2 ** 62)                 # torch's device generator: fresh words on every replay
+            seed = _seam.fresh_seed(self.seed.device, out=self.seed)
         into = out
         if self.augment is not None:
             if self._staging is None:

@@ -226,20 +226,10 @@ class DeviceKittiFrames(DeviceFrustumKitti):
         """One launch.  As `DeviceFrustumKitti.assemble`, plus `params` (B, 12) fp64, the parity rows of the box perturbation (needed
         with `choices` unless shift_ratio is 0), and `draws_out` (an `empty_draws` dict) to record every draw."""
         self._finalise()
-        self._backend()
-        order, cursor, b = self._indices(indices, order, cursor, batch_size)
-        if out is None:
-            out = self.empty_batch(b)
-        else:
-            self._check_out(out, self._describe(b))
-        choices = self._draw(choices, (b, self.num_points), torch.int32, 'choices')
+        _, order, cursor, b, out, choices = self._begin(indices, out, order, cursor, batch_size, choices)
         params = self._draw(params, (b, PARAMS), torch.float64, 'params')
         flip, shift = self._draw(flip, (b,), torch.float64, 'flip'), self._draw(shift, (b,), torch.float64, 'shift')
-        if choices is None and (params is not None or flip is not None or shift is not None):
-            raise ValueError('`params` / `flip` / `shift` draws without `choices`: parity mode takes every draw from the caller')
-        if choices is not None and ((self.shift_ratio != 0.0 and params is None) or (self.random_flip and flip is None)
-                                    or (self.random_shift and shift is None)):
-            raise ValueError('parity mode takes every draw from the caller: `params` (B, 12) / `flip` (B) / `shift` (B) fp64 are missing')
+        self._parity(choices, params=(params, self.shift_ratio != 0.0), flip=(flip, self.random_flip), shift=(shift, self.random_shift))
         seed = None if choices is not None else self._seed(seed)
         if draws_out is None:
             params_out, used = self.draws(b)

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .modules.functional.backend import _run
+from .modules.functional.backend import _device_call as _call, check_seed, fresh_seed
 
 __all__ = ['Calibration', 'FrameFrustums', 'read_scan', 'frustum_angle', 'random_shift_box2d', 'box_corners', 'box_table', 'project_scan',
            'extract_frustums', 'frame_batch', 'detect_frame', 'kitti_label_lines', 'copies_made', 'BOX_COLUMNS']
@@ -50,14 +50,6 @@ def _device():
     if not torch.cuda.is_available():
         raise RuntimeError('KITTI frames need a GPU and the native library -- there is no CPU implementation')
     return torch.device('cuda', torch.cuda.current_device())
-
-
-def _call(name, ref, *args):
-    """One pvcnn_frame_* call on `ref`'s device and torch's current stream: tensors as device pointers, None as NULL, floats as doubles."""
-    for a in args:
-        if isinstance(a, torch.Tensor) and (a.device != ref.device or not a.is_contiguous()):
-            raise ValueError(f'{name}: contiguous tensors on one device expected')
-    _run(getattr(_lib.load(), 'pvcnn_' + name), name, ref, *(a if a is None or isinstance(a, (torch.Tensor, float)) else int(a) for a in args))
 
 
 class Calibration:
@@ -342,10 +334,8 @@ def frame_batch(scan, calib, boxes_2d, image_size, class_ids=None, *, num_points
         if tuple(choices.shape) != (m, num_points):
             raise ValueError(f'choices of shape {(m, num_points)} expected, got {tuple(choices.shape)}')
         seed = None
-    elif seed is None:
-        seed = torch.randint(0, 2 ** 62, (2,), device=dev, dtype=torch.int64)          # device generator: no sync
-    elif not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or seed.numel() < 2 or seed.device != dev:
-        raise ValueError('seed = two int64 words on the device')
+    else:
+        seed = fresh_seed(dev) if seed is None else check_seed(seed, dev)
     rows, uv, in_image = _project(x, calib, image_size, clip_distance, count)
     if m:
         mask, _, prefix, counts = _count(rows, uv, in_image, table, False)

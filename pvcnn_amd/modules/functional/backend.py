@@ -112,6 +112,33 @@ def _run(fn, label, ref, *args):
         _lib.check(fn(*conv, s), label)
 
 
+def _device_call(name, ref, *args, lib=None, error=ValueError):
+    """One pvcnn_<name> call (of `lib`, default the loaded library) on `ref`'s device and torch's current stream (`_run`): tensors
+    (contiguous, on that device, else `error`) as device pointers, None as NULL, floats as doubles, everything else as an int."""
+    for a in args:
+        if isinstance(a, torch.Tensor) and (a.device != ref.device or not a.is_contiguous()):
+            raise error(f'{name}: contiguous tensors on one device expected')
+    _run(getattr(lib or _lib.load(), 'pvcnn_' + name), name, ref, *(a if a is None or isinstance(a, (torch.Tensor, float)) else int(a) for a in args))
+
+
+def fresh_seed(device, generator=None, out=None):
+    """The two int64 words that key a device draw stream (include/pvcnn_hip.h, "Device draws"), from torch's generator of `device`
+    (or from `generator`, on its own device): no host synchronisation, `torch.manual_seed` governs them.  `out`: two device words
+    redrawn in place -- inside a captured step, fresh words on every replay."""
+    if out is not None:
+        return out.random_(0, 2 ** 62)
+    gdev = generator.device if generator is not None else device
+    return torch.randint(0, 2 ** 62, (2,), dtype=torch.int64, device=gdev, generator=generator).to(device)
+
+
+def check_seed(seed, device=None):
+    """-> seed, or ValueError unless it is two (or more) contiguous int64 words on `device` (default: on any GPU)."""
+    if not isinstance(seed, torch.Tensor) or seed.dtype != torch.int64 or seed.numel() < 2 or not seed.is_contiguous() \
+            or (seed.device != device if device is not None else not seed.is_cuda):
+        raise ValueError('seed = two int64 words on the device')
+    return seed
+
+
 def _mean_rstd(c, device):
     """The uninitialised (mean, rstd) pair of a BatchNorm over c channels."""
     return torch.empty((c,), dtype=torch.float32, device=device), torch.empty((c,), dtype=torch.float32, device=device)
@@ -219,14 +246,11 @@ class HipBackend:
     has_batch_assembly = True
 
     def batch_launch(self, entry, ref, *args):
-        """One pvcnn_batch_* launch on `ref`'s device and torch's current stream.  Tensors among `args` are passed as device
-        pointers (None as NULL) and must live on that device, contiguous; ints go through as they are."""
-        for a in args:
+        """One pvcnn_batch_* launch on `ref`'s device and torch's current stream (`_device_call`); a tensor off the GPU is refused."""
+        for a in (*args, ref):
             if isinstance(a, torch.Tensor):
                 _dev(a, entry)
-                _shape(a.is_contiguous() and a.device == ref.device, f'{entry}: contiguous tensors on one device expected')
-        _dev(ref, entry)
-        _run(getattr(self.lib, 'pvcnn_' + entry), entry, ref, *(a if a is None or isinstance(a, torch.Tensor) else int(a) for a in args))
+        _device_call(entry, ref, *args, lib=self.lib, error=RuntimeError)
 
     # ---- augmentation of an assembled batch (csrc/augment.hip; pvcnn_amd/augment.py checks shapes and owns the tensors) ----------
     has_augment = True

@@ -4,6 +4,7 @@ import torch
 from torch.autograd import Function
 
 from ._autograd import native, amp_fwd, amp_bwd
+from .backend import fresh_seed
 
 __all__ = ['gather', 'furthest_point_sample', 'logits_mask', 'numpy_choices']
 
@@ -87,8 +88,7 @@ def logits_mask(coords, logits, num_points_per_object, rng=None, choices=None):
     if on_device and choices is not None:
         picks = be.mask_select(mask.contiguous(), m, choices=choices.to(device=coords.device, dtype=torch.int32).contiguous())
     elif on_device and mode == 'device':
-        seed = torch.randint(0, 2 ** 62, (2,), device=coords.device, dtype=torch.int64)     # device generator: no sync
-        picks = be.mask_select(mask.contiguous(), m, seed=seed)
+        picks = be.mask_select(mask.contiguous(), m, seed=fresh_seed(coords.device))
     else:
         picks = torch.zeros((nb, m), device=coords.device, dtype=torch.int32)
         for bi in range(nb):

@@ -27,7 +27,7 @@ import torch
 
 from . import _lib
 from .evaluate import SceneVotes, s3dis_file_votes
-from .modules.functional.backend import _run
+from .modules.functional.backend import _device_call as _call, fresh_seed
 
 __all__ = ['RoomWindows', 'prepare_room', 'segment_room', 'copies_made', 'COPIES_PER_PASS']
 
@@ -46,14 +46,6 @@ def _read(t):
     global _copies
     _copies += 1
     return t.cpu().tolist()
-
-
-def _call(name, ref, *args):
-    """One pvcnn_room_* call on `ref`'s device and torch's current stream: tensors as device pointers, None as NULL, floats as doubles."""
-    for a in args:
-        if isinstance(a, torch.Tensor) and (a.device != ref.device or not a.is_contiguous()):
-            raise ValueError(f'{name}: contiguous tensors on one device expected')
-    _run(getattr(_lib.load(), 'pvcnn_' + name), name, ref, *(a if a is None or isinstance(a, (torch.Tensor, float)) else int(a) for a in args))
 
 
 def _device_points(xyzrgb):
@@ -183,8 +175,7 @@ def prepare_room(xyzrgb, labels=None, *, max_num_points=8192, block_size=1.5, gr
         raise ValueError('a merged block spans more than 2^21 cells along one axis: grid_size is too small for this room')
 
     # step 4c: the resampling fill and the block shuffle's keys
-    gdev = generator.device if generator is not None else dev
-    seed = torch.randint(0, 2 ** 62, (2,), dtype=torch.int64, device=gdev, generator=generator).to(dev)
+    seed = fresh_seed(dev, generator)
     entry_point, entry_block = torch.empty((num_entries,), **i32), torch.empty((num_entries,), **i32)
     entry_key = torch.empty((num_entries,), **i64)
     _call('room_fill', x, perm, sorted_block, point_cell, cell_start, cell_out_start, block_tables, status, n, g, num_entries, seed,
