@@ -1141,6 +1141,41 @@ PVCNN_API int pvcnn_frame_store_batch(const float *rows, const double *uv, const
                                       int64_t *class_id, double *params_out, int32_t *used, int32_t *choices_out, double *flip_out,
                                       double *shift_out, void *stream);
 
+/* ---- Shapes on the device: exact k-nearest neighbours over packed ragged clouds and PCA surface normals from them (csrc/shapes.hip,
+ * pvcnn_amd/shapes.py; an additive group: the ABI version does not move).  The reference's ShapeNet recipes read xyz, a surface normal
+ * and a one-hot shape id per point, and only the benchmark's text files carry those normals; these entry points compute them from xyz.
+ * THIS is the definition, restated in numpy by tests/shapes_truth.py.
+ *
+ * Layout (data._Store's): rows (R, ld) fp32, ld >= 3, xyz in the first three columns; offsets (W + 1) int64, cloud w owning rows
+ * offsets[w] .. offsets[w + 1], n_w >= 1 of them, offsets[0] = 0, offsets[W] = R; R <= 2^31 - 64.
+ *
+ * pvcnn_k_nearest, 1 <= k <= PVCNN_K_NEAREST_MAX_K: for a query row i and a candidate row j of the same cloud
+ *   dx = fl32(xj - xi), dy, dz likewise;  d = fl32(fl32(fl32(dx dx) + fl32(dy dy)) + fl32(dz dz))
+ *   (one rounding per operation, no fused multiply-add).  out (R, k) int32: the min(k, n_w) candidates smallest in (d, j), ascending,
+ *   as positions INSIDE the cloud (0 .. n_w - 1); the query is a candidate like any other (d = 0); columns past n_w hold -1.  Finite
+ *   coordinates are the contract: with others the result is unspecified, but every index written lies in [-1, n_w) and nothing is read
+ *   out of range.  The search is exhaustive, O(n_w^2) per cloud: the caller bounds n_w (pvcnn_amd.shapes: max_cloud_points).
+ *
+ * pvcnn_shape_normals: knn (R, k) as above.  For a point with c = min(k, n_w) neighbours: m = their mean, C = sum (p - m)(p - m)^T;
+ *   the normal is a unit eigenvector of C's smallest eigenvalue lambda_0, the curvature lambda_0 / trace(C); with c < 3 or
+ *   trace(C) == 0 the normal is (0, 0, 0) and the curvature 0.  Mean and C are accumulated in fp64 over the table's columns in order, the
+ *   eigenvector comes from a fixed number of Jacobi sweeps in fp64 (csrc/eig3.h) and is rounded to fp32 once.  ref (W, 3) fp32, one
+ *   point per cloud, and mode: 0 sign unspecified (ref may be NULL); 1 outward, n . (p - ref_w) >= 0; 2 towards, n . (ref_w - p) >= 0
+ *   (the product of the ROUNDED normal, in fp64; a zero product keeps the solver's sign).  normals (R, 3) fp32; curvature (R) fp32 or
+ *   NULL.  Table entries outside [0, n_w) are skipped (and not counted in c).
+ *
+ * pvcnn_cloud_centroids: out (W, 3) fp32 = the fp64 mean of each cloud's xyz, rounded once (the `ref` of mode 1).  One wave per cloud:
+ *   lane l adds rows l, l + 64, ... in order, then the butterfly over the lane bits 5 .. 0: the same bits for the same input.
+ *
+ * Plain launches on `stream`: no allocation, no synchronisation, no atomics, no workspace; they can be captured. */
+#define PVCNN_K_NEAREST_MAX_K 64
+PVCNN_API int pvcnn_k_nearest(const float *rows, long long R, int ld, const int64_t *offsets, long long W, int k, int32_t *out,
+                              void *stream);
+PVCNN_API int pvcnn_shape_normals(const float *rows, long long R, int ld, const int64_t *offsets, long long W, const int32_t *knn,
+                                  int k, const float *ref, int mode, float *normals, float *curvature, void *stream);
+PVCNN_API int pvcnn_cloud_centroids(const float *rows, long long R, int ld, const int64_t *offsets, long long W, float *out,
+                                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

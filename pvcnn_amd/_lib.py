@@ -193,6 +193,10 @@ SIGNATURES = {
     'pvcnn_augment_draw': (_i, [_i, _i] + [_d] * 10 + [_vp, _vp, _vp]),
     'pvcnn_augment_apply': (_i, [_vp, _ll, _vp, _ll, _i, _i, _i, _vp, _i, _vp, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _ll, _vp, _ll, _vp, _vp,
                                  _vp]),
+    # shapes on the device (csrc/shapes.hip): k nearest neighbours over packed clouds, PCA normals, per-cloud centroids
+    'pvcnn_k_nearest': (_i, [_vp, _ll, _i, _vp, _ll, _i, _vp, _vp]),
+    'pvcnn_shape_normals': (_i, [_vp, _ll, _i, _vp, _ll, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    'pvcnn_cloud_centroids': (_i, [_vp, _ll, _i, _vp, _ll, _vp, _vp]),
 }
 
 _lib = None

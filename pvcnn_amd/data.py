@@ -286,16 +286,7 @@ class DeviceShapeNet(_Store):
 
     def __init__(self, clouds, shape_ids, num_points, with_normal=True, with_one_hot_shape_id=True, normalize=True, jitter=True,
                  device=None):
-        shape_ids = np.asarray(shape_ids, dtype=np.int64).reshape(-1)
-        if len(clouds) != shape_ids.shape[0]:
-            raise ValueError('one shape id per cloud expected')
-        if shape_ids.size and (shape_ids.min() < 0 or shape_ids.max() >= self.num_shapes):
-            raise ValueError(f'shape ids must lie in [0, {self.num_shapes})')
-        if int(num_points) < 1:
-            raise ValueError('num_points must be positive')
-        self.num_points = int(num_points)
-        self.with_normal, self.with_one_hot_shape_id = bool(with_normal), bool(with_one_hot_shape_id)
-        self.normalize, self.jitter = bool(normalize), bool(jitter)
+        shape_ids = self._configure(len(clouds), shape_ids, num_points, with_normal, with_one_hot_shape_id, normalize, jitter)
         rows, labels = [], []
         for cloud in clouds:
             cloud = _numpy(cloud)
@@ -307,9 +298,64 @@ class DeviceShapeNet(_Store):
                 coords = self.normalize_point_cloud(coords)
             rows.append(np.concatenate([coords, data[:, 3:6]], axis=1))
             labels.append(data[:, -1].astype(np.int64))
+        self._pack_shapes(rows, labels, shape_ids, device)
+
+    def _configure(self, num_clouds, shape_ids, num_points, with_normal, with_one_hot_shape_id, normalize, jitter):
+        """The checks and the flags every way of building the store shares -> shape_ids (W,) int64 numpy."""
+        shape_ids = np.asarray(shape_ids, dtype=np.int64).reshape(-1)
+        if num_clouds != shape_ids.shape[0]:
+            raise ValueError('one shape id per cloud expected')
+        if shape_ids.size and (shape_ids.min() < 0 or shape_ids.max() >= self.num_shapes):
+            raise ValueError(f'shape ids must lie in [0, {self.num_shapes})')
+        if int(num_points) < 1:
+            raise ValueError('num_points must be positive')
+        self.num_points = int(num_points)
+        self.with_normal, self.with_one_hot_shape_id = bool(with_normal), bool(with_one_hot_shape_id)
+        self.normalize, self.jitter = bool(normalize), bool(jitter)
+        return shape_ids
+
+    def _pack_shapes(self, rows, labels, shape_ids, device):
         self._pack(rows, labels, device)
         self.shape_ids = torch.from_numpy(shape_ids.astype(np.int32)).to(self.device)
         self._tables = self._tables + ['shape_ids']
+
+    @classmethod
+    def from_clouds(cls, clouds, labels, shape_ids, num_points, *, k=16, orient='outward', with_normal=True,
+                    with_one_hot_shape_id=True, normalize=True, jitter=True, device=None):
+        """From raw clouds WITHOUT normals: clouds[i] (n_i, 3) xyz, labels[i] (n_i,) part labels, one shape id per cloud.  The
+        coordinates are normalised on the host exactly as the constructor normalises them; the normals of the whole split are then
+        computed on the packed rows by ONE k_nearest launch and ONE shape_normals launch (pvcnn_amd.shapes: PCA over the k nearest
+        points, oriented by `orient`; 'outward' adds the centroid launch) and written into the store's normal columns.  The store is the
+        one the constructor builds from the (n_i, 7) arrays [xyz, those normals, label]: `assemble`, `DeviceLoader` and `Augment` work
+        on it unchanged.  with_normal=False stores zero normals (nothing reads them) and launches nothing.  A store on the CPU takes
+        the torch formulation of the same definitions."""
+        from . import shapes as _shapes
+        if len(labels) != len(clouds):
+            raise ValueError('one label array per cloud expected')
+        self = cls.__new__(cls)
+        shape_ids = self._configure(len(clouds), shape_ids, num_points, with_normal, with_one_hot_shape_id, normalize, jitter)
+        k = _shapes._check_k(k)
+        rows, label_list = [], []
+        for cloud, label in zip(clouds, labels):
+            cloud, label = _numpy(cloud), _numpy(label).reshape(-1)
+            if cloud.ndim != 2 or cloud.shape[1] != 3:
+                raise ValueError(f'clouds of shape (n, 3) expected, got {cloud.shape}')
+            if label.shape[0] != cloud.shape[0]:
+                raise ValueError(f'{cloud.shape[0]} labels expected, got {label.shape[0]}')
+            data = np.zeros((cloud.shape[0], 7), dtype=np.float32)          # the constructor's array: same layout, same arithmetic
+            data[:, :3] = cloud
+            coords = data[:, :3]
+            if self.normalize:
+                coords = self.normalize_point_cloud(coords)
+            rows.append(np.concatenate([coords, data[:, 3:6]], axis=1))
+            label_list.append(label.astype(np.float32).astype(np.int64))    # (labels reach the constructor through the fp32 array)
+        self._pack_shapes(rows, label_list, shape_ids, device)
+        if self.with_normal:
+            host = self.offsets.cpu().numpy() if self.offsets.is_cuda else self.offsets.numpy()
+            _shapes._check_sizes(host, _shapes.MAX_CLOUD_POINTS)
+            normals, _ = _shapes._normals_packed(self.rows, self.offsets, host, k, orient)
+            self.rows[:, 3:6] = normals
+        return self
 
     @staticmethod
     def normalize_point_cloud(points):

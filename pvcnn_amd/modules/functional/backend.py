@@ -72,6 +72,12 @@ def _shape(cond, msg):
         raise RuntimeError(msg)
 
 
+def _arg(cond, msg):
+    """_shape for the entry points whose messages their own tests trip (tests/test_gpu_shapes.py), not the recorded call logs."""
+    if not cond:
+        raise RuntimeError(msg)
+
+
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else ctypes.c_void_p(None)
 
@@ -1609,6 +1615,67 @@ class HipBackend:
         _run(self.lib.pvcnn_kitti_ap_stats, 'kitti_ap_stats', p.gt_off, *args, thresholds, counts, int(metric), int(bool(compute_aos)), pr,
              workspace, nbytes)
         return pr
+
+    # ---- shapes on the device (csrc/shapes.hip; include/pvcnn_hip.h "Shapes on the device"; pvcnn_amd/shapes.py owns the policy) ----
+    has_shapes = True
+    K_NEAREST_MAX_K = 64
+
+    @staticmethod
+    def _packed(rows, offsets, who):
+        """rows (R, ld >= 3) fp32 with unit column stride (a column slice of a wider store is fine), offsets (W + 1,) int64
+        -> (R, ld, W)."""
+        _dev(rows, 'rows'); _dev(offsets, 'offsets')
+        _arg(rows.dim() == 2 and rows.dtype == torch.float32 and rows.shape[1] >= 3 and (rows.shape[0] <= 1 or rows.stride(0) >= rows.shape[1])
+               and rows.stride(1) == 1, f'{who}: rows (R, >= 3) float32 with contiguous columns expected')
+        _arg(offsets.dim() == 1 and offsets.dtype == torch.int64 and offsets.numel() >= 1 and offsets.is_contiguous()
+               and offsets.device == rows.device, f'{who}: offsets (W + 1,) int64 on the rows\' device expected')
+        return rows.shape[0], (rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]), offsets.numel() - 1
+
+    @staticmethod
+    def _shapes_out(out, shape, dtype, device, who):
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=device)
+        _arg(tuple(out.shape) == tuple(shape) and out.dtype == dtype and out.device == device and out.is_contiguous(),
+               f'{who}: out= must be a contiguous {dtype} tensor of shape {tuple(shape)} on {device}')
+        return out
+
+    def k_nearest(self, rows, offsets, k, out=None):
+        """-> (R, k) int32: per row the min(k, n_w) nearest rows of its own cloud, ascending in (distance, position), as positions inside
+        the cloud; -1 beyond n_w.  One launch, nothing read back: capturable (give `out=` for a static buffer)."""
+        r, ld, w = self._packed(rows, offsets, 'k_nearest')
+        k = int(k)
+        _arg(1 <= k <= self.K_NEAREST_MAX_K, f'k_nearest: k in [1, {self.K_NEAREST_MAX_K}] expected')
+        out = self._shapes_out(out, (r, k), torch.int32, rows.device, 'k_nearest')
+        _run(self.lib.pvcnn_k_nearest, 'k_nearest', rows, rows, r, ld, offsets, w, k, out)
+        return out
+
+    def shape_normals(self, rows, offsets, knn, ref=None, mode=0, want_curvature=False, out=None, out_curvature=None):
+        """-> (normals (R, 3) fp32, curvature (R,) fp32 or None) from the neighbour table knn (R, k) int32; ref (W, 3) fp32 and
+        mode 1 (outward from ref) / 2 (towards ref), or mode 0: sign as the solver leaves it.  One launch."""
+        r, ld, w = self._packed(rows, offsets, 'shape_normals')
+        _i32(knn, 'knn')
+        _arg(knn.dim() == 2 and knn.shape[0] == r and 1 <= knn.shape[1] <= self.K_NEAREST_MAX_K and knn.device == rows.device,
+               'shape_normals: knn (R, k) int32 with k in [1, 64] expected')
+        mode = int(mode)
+        _arg(mode in (0, 1, 2), 'shape_normals: mode 0, 1 or 2 expected')
+        if mode:
+            _arg(ref is not None, 'shape_normals: an oriented mode needs ref (W, 3)')
+            _f32(ref, 'ref')
+            _arg(tuple(ref.shape) == (w, 3) and ref.device == rows.device, 'shape_normals: ref (W, 3) float32 expected')
+        normals = self._shapes_out(out, (r, 3), torch.float32, rows.device, 'shape_normals')
+        curvature = None
+        if want_curvature or out_curvature is not None:
+            curvature = self._shapes_out(out_curvature, (r,), torch.float32, rows.device, 'shape_normals')
+        _run(self.lib.pvcnn_shape_normals, 'shape_normals', rows, rows, r, ld, offsets, w, knn, knn.shape[1], ref if mode else None, mode,
+             normals, curvature)
+        return normals, curvature
+
+    def cloud_centroids(self, rows, offsets, out=None):
+        """-> (W, 3) fp32: the fp64 mean of every cloud's xyz, rounded once.  One launch."""
+        r, ld, w = self._packed(rows, offsets, 'cloud_centroids')
+        out = self._shapes_out(out, (w, 3), torch.float32, rows.device, 'cloud_centroids')
+        _run(self.lib.pvcnn_cloud_centroids, 'cloud_centroids', rows, rows, r, ld, offsets, w, out)
+        return out
 
 
 class _WeightBank:
