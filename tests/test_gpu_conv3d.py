@@ -205,7 +205,7 @@ def test_conv3d_backward_weight_f16x2(hip, b, ci, co, r):
 def test_voxel_conv_autograd_in_f16x2_matches_fp64(hip):
     """The default arithmetic end to end through the autograd function (forward, backward-data, backward-weight, bias)."""
     from pvcnn_amd.modules.pvconv import _VoxelConv3d
-    assert hip.conv_math == 'f16x2' or True
+    assert hip.conv_math == 'f16x2'             # (the other modes through autograd: tests/test_gpu_math_modes.py)
     torch.manual_seed(0)
     mine = _VoxelConv3d(24, 40, 3, stride=1, padding=1).to(DEV)
     theirs = torch.nn.Conv3d(24, 40, 3, stride=1, padding=1).to(DEV).double()

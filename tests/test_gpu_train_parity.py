@@ -196,6 +196,12 @@ def _report(label, res_g, res_c, res_t):
 def test_pvconv_train_gradients_match_the_oracle_stack(hip, oracle, cin, cout, r, n, se, normalize):
     """ONE PVConv, train mode: loss, input gradient, every parameter gradient and the updated BatchNorm running
     statistics of the HIP path within 1e-4 (per tensor, relative to the tensor's largest entry) of the oracle stack."""
+    check_pvconv_train_gradients(oracle, cin, cout, r, n, se, normalize)
+
+
+def check_pvconv_train_gradients(oracle, cin, cout, r, n, se, normalize, mode=''):
+    """The body of test_pvconv_train_gradients_match_the_oracle_stack, callable under another arithmetic of the live backend
+    (tests/test_gpu_math_modes.py; `mode` only extends the printed label) -> the rows of _report."""
     from pvcnn_amd.modules import PVConv
     from pvcnn_amd import workload
     b = 3
@@ -212,7 +218,7 @@ def test_pvconv_train_gradients_match_the_oracle_stack(hip, oracle, cin, cout, r
     def loss_fn(out, tgt):
         return (out[0] * tgt).mean() + out[0].square().mean()
 
-    label = f'PVConv({cin}->{cout}, R={r}, N={n}, se={se}, normalize={normalize})'
+    label = f'PVConv({cin}->{cout}, R={r}, N={n}, se={se}, normalize={normalize})' + mode
     # the fp32 checker's Conv3d on ATen's own CPU kernels, not oneDNN's: oneDNN's weight gradient sums in an order chosen by the host's
     # ISA, and on AVX-512 hosts the 64 -> 64 layer at R = 32 lands 5.9e-4 (per tensor) from the fp64 truth through the train-mode
     # BatchNorm behind it -- the checker, not the HIP path (1.5e-6), would decide this test; ATen's kernels keep it within ~1e-6 of the truth
@@ -222,6 +228,7 @@ def test_pvconv_train_gradients_match_the_oracle_stack(hip, oracle, cin, cout, r
     assert abs(res[0][0] - res[1][0]) <= TOL_LOSS * max(abs(res[1][0]), 1.0)
     bad = [(k, a) for k, a, _, _ in rows if a > TOL_LAYER]
     assert not bad, f'{label}: {bad[:6]}'
+    return rows
 
 
 FLOOR_T = 1e-4         # per-tensor floor of the strict bar (max-norm, relative to the tensor's largest entry)

@@ -476,6 +476,67 @@ def test_pointwise_conv_routes_by_the_two_size_bars(monkeypatch):
         assert torch.allclose(x.grad, x2.grad, atol=1e-5) and torch.allclose(w.grad, w2.grad, atol=1e-4) and torch.allclose(bias.grad, b2.grad, atol=1e-4)
 
 
+@pytest.mark.parametrize('mode,nsplit', [('f16x2', 2), ('bf16x3', 3), ('fp32', 0), ('tf32', 0), (None, 0)])
+def test_pw_nsplit_and_the_routes_follow_every_mode_string(monkeypatch, mode, nsplit):
+    """functional/pwconv.py pw_nsplit per `pw_math`: f16x2 -> 2, bf16x3 -> 3, fp32 -> 0; a string the table does not hold -- and a
+    backend without the attribute -- falls back to the fp32 kernels (`PW_NSPLIT.get(..., 0)`); below `pw_split_min_macs` it is 0 in
+    every mode.  pointwise_conv then takes that family, and only f16x2 measures amax buffers or takes the f16x2 backward-weight."""
+    from pvcnn_amd.modules.functional import backend as seam
+    from pvcnn_amd.modules.functional.pwconv import pointwise_conv, pw_nsplit
+    fake = _PwRouteStandIn()
+    if mode is None:
+        monkeypatch.delattr(_PwRouteStandIn, 'pw_math')
+    else:
+        fake.pw_math = mode
+    monkeypatch.setattr(seam, '_backend', fake)
+    assert nsplit == seam.HipBackend.PW_NSPLIT.get(mode if mode is not None else 'fp32', 0) == fake.PW_NSPLIT.get(mode, 0)
+    torch.manual_seed(4)
+    below, at = (1, 4, 4, 64), (2, 8, 8, 32)                      # 1 Ki multiply-adds; 4 Ki = the stand-in's bar exactly (`macs < bar`)
+    assert below[0] * below[1] * below[2] * below[3] < fake.pw_split_min_macs == at[0] * at[1] * at[2] * at[3]
+    split = {2: ['pw_amax', 'forward_split2', 'pw_amax', 'bwd_data_split2', 'wgrad_fp32'],       # (4 Ki < the 64 Ki backward-weight bar)
+             3: ['forward_split3', 'bwd_data_split3', 'wgrad_fp32'], 0: ['forward_fp32', 'bwd_data_fp32', 'wgrad_fp32']}
+    for (b, ci, co, n), want_nsplit in ((below, 0), (at, nsplit)):
+        x = torch.randn(b, ci, n, requires_grad=True)
+        w = torch.randn(co, ci, 1, requires_grad=True)
+        assert pw_nsplit(x, w.view(co, ci)) == want_nsplit
+        fake.calls.clear()
+        pointwise_conv(x, w, None).sum().backward()
+        assert fake.calls == split[want_nsplit], (mode, fake.calls)
+    big = (2, 32, 32, 64)                                         # above both bars: the f16x2 backward-weight kernel in f16x2 mode alone
+    x, w = torch.randn(*big[:2], big[3], requires_grad=True), torch.randn(big[2], big[1], 1, requires_grad=True)
+    fake.calls.clear()
+    pointwise_conv(x, w, None).sum().backward()
+    assert fake.calls[-1] == ('wgrad_f16' if nsplit == 2 else 'wgrad_fp32'), (mode, fake.calls)
+
+
+@pytest.mark.parametrize('mode,nsplit', [('f16x2', 2), ('bf16x3', 3), ('fp32', 0), ('tf32', 0), (None, 0)])
+def test_conv_nsplit_and_the_amax_hand_over_follow_every_mode_string(monkeypatch, mode, nsplit):
+    """functional/conv3d.py conv_nsplit per `conv_math` (same table, same fallback: `CONV_NSPLIT.get(..., 0)`; 0 without the split
+    kernels), and functional/bnact.py _amax_seg_for: a BatchNorm pass emits an amax table only for an f16x2 consumer of ITS kind."""
+    from pvcnn_amd.modules.functional import backend as seam
+    from pvcnn_amd.modules.functional.bnact import _amax_seg_for
+    from pvcnn_amd.modules.functional.conv3d import conv_nsplit
+
+    class Fake:
+        has_conv3d_split = has_pwconv_split = True
+        CONV_NSPLIT = {'f16x2': 2, 'bf16x3': 3, 'fp32': 0}
+        PW_AMAX_SEG, BNACT_AMAX_MAX_SEG = 256, 256
+        pw_math = 'f16x2'
+    fake = Fake()
+    if mode is not None:
+        fake.conv_math = mode
+    monkeypatch.setattr(seam, '_backend', fake)
+    assert nsplit == seam.HipBackend.CONV_NSPLIT.get(mode if mode is not None else 'fp32', 0) == conv_nsplit()
+    grid, points = (2, 8, 12, 12, 12), (2, 8, 300)
+    assert _amax_seg_for(grid, True) == (12 if mode == 'f16x2' else 0)          # the Conv3d's z row, for an f16x2 Conv3d only
+    assert _amax_seg_for(points, True) == 256                                   # ... whatever the Conv3d's mode: the 1x1's own
+    assert _amax_seg_for(grid, False) == 0 and _amax_seg_for(points, False) == 0
+    fake.pw_math, fake.conv_math = (mode or 'fp32'), 'f16x2'                    # and the reverse pair
+    assert _amax_seg_for(points, True) == (256 if mode == 'f16x2' else 0) and _amax_seg_for(grid, True) == 12
+    fake.has_conv3d_split = False
+    assert conv_nsplit() == 0
+
+
 def test_classifier_head_and_pooling_fall_back_to_the_modules_on_cpu():
     """workload._classify (fused Dropout, last Conv1d on the package's GEMM) and functional.pooling.neighbor_max (csrc/pool.hip) are
     GPU paths: on CPU tensors they ARE nn.Sequential.forward / torch.max, bit for bit, in train and eval mode."""
