@@ -1031,6 +1031,51 @@ PVCNN_API int pvcnn_dml_pair_bwd(const float *a, long long a_bstride, const floa
                                  long long t_bstride, const float *weight, const float *grad_out, long long B, int C, long long S,
                                  long long ignore_index, int side, const void *workspace, float *grad, void *stream);
 
+/* The Lovasz-Softmax criterion (csrc/lovasz.hip; Berman et al., CVPR 2018, per_image; an additive group: the ABI version does not
+ * move).  THIS is its definition; tests/lovasz_truth.py restates it in numpy.
+ *   p       fp32 (B, C, S) probabilities, laid out like pvcnn_xent_*'s x (class rows contiguous, batch stride p_bstride >= C * S):
+ *           the caller's own, or softmax(x) over the classes as pvcnn_lovasz_probs writes it (packed, expf(x_c - max) / sum in fp32);
+ *   target  int64 (B, S), batch stride t_bstride >= S.  A point is LIVE when its target is not ignore_index and lies in [0, C).  A
+ *           target outside [0, C) that is not ignore_index is treated as ignored and counted (pvcnn_xent_*'s bad_targets contract).
+ * Per cloud b and class c, over the live points i:  fg_i = (target_i == c),  G = the number of foreground points,
+ *   e_i = fg_i ? 1.0f - p_i : p_i                                                (ONE fp32 IEEE subtraction)
+ *   the points are ordered by e descending, ties by ascending point index; walking the order with position i = 1, 2, ... and
+ *   cf = the foreground points among the first i:  I = G - cf,  U = G + i - cf  (integers, U >= 1); the Jaccard index after i
+ *   elements is 1 - I / U and its step, in closed form (never a difference of two indices), in fp64:
+ *     step_i = 1 / U for a foreground element,  I / (U (U - 1)) for a background element,
+ *     G == 0: step_1 = 1, all others 0                                            (the steps are >= 0 and add up to 1)
+ *   loss(b, c) = sum_i e_(i) step_i, added in fp64 in a fixed order.
+ * Cloud loss: the mean of loss(b, c) over the COUNTED classes -- classes_all == 0 ('present'): those with G > 0; classes_all != 0
+ *   ('all'): all C classes of a cloud that has a live point; a cloud without counted classes gives 0 (k_b = counted classes).
+ * loss[0] = the mean of the cloud losses over all B clouds, rounded to fp32 once.
+ * Gradient: the order is a constant, so d loss / d e_(i) = step_i / (k_b B); d / d p = -that at a foreground point, +that at a
+ *   background one; for logits the softmax Jacobian follows, dx_j = p_j (g_j - sum_c p_c g_c).  Dead points and classes that are
+ *   not counted get exact zeros; every element is written.
+ * Launches, in this order, with the same arguments:
+ *   pvcnn_lovasz_probs     (logits only) p (B, C, S) packed <- softmax(x);
+ *   pvcnn_lovasz_sort      grid (C, B), one workgroup per list, the list sorted in LDS (S <= 16384); grad_p (B, C, S) packed <-
+ *                          -step / +step at every live point of a counted class (d loss(b, c) / d p), zeros elsewhere;
+ *   pvcnn_lovasz_finalize  one workgroup, fp64: loss[0]; bad_targets (one int64 in device memory, or NULL) += the out-of-range
+ *                          count (a plain read-modify-write by one thread, as pvcnn_xent_finalize's);
+ *   pvcnn_lovasz_bwd       grad (B, C, S) packed, every element: with g_c = grad_out[0] (one fp32 in device memory) * scale[b] *
+ *                          grad_p[b][c][.]:  probas != 0: g_c (the gradient for the probabilities);  probas == 0: p_c (g_c - sum_j p_j g_j),
+ *                          the products, the sum and the difference formed in fp64 and rounded to fp32 once (at a saturated point the
+ *                          difference cancels to the order of 1 - max p).
+ *   workspace  pvcnn_lovasz_workspace_bytes(B, C, S) bytes, 16-byte aligned, written by sort and finalize, read by finalize and bwd:
+ *           scale (B) fp32 = 1 / (k_b B) (0 for a cloud without counted classes), padded to 16 bytes | (B, C, 4) fp64: loss(b, c),
+ *           G, the cloud's live points, the cloud's out-of-range targets.
+ *           The query is host-only and returns 0 for what the kernels refuse: S > 16384, B > 65535, sizes they do not index.
+ * A bad value is refused (-1, no launch) before any pointer is looked at.  No allocation, no host synchronisation.  Deterministic:
+ * no float atomics, the same bits for the same inputs. */
+PVCNN_API size_t pvcnn_lovasz_workspace_bytes(long long B, int C, long long S);
+PVCNN_API int pvcnn_lovasz_probs(const float *x, long long x_bstride, long long B, int C, long long S, float *p, void *stream);
+PVCNN_API int pvcnn_lovasz_sort(const float *p, long long p_bstride, const long long *target, long long t_bstride, long long B, int C,
+                                long long S, long long ignore_index, int classes_all, void *workspace, float *grad_p, void *stream);
+PVCNN_API int pvcnn_lovasz_finalize(long long B, int C, long long S, int classes_all, void *workspace, float *loss,
+                                    long long *bad_targets, void *stream);
+PVCNN_API int pvcnn_lovasz_bwd(const float *p, long long p_bstride, const float *grad_p, const float *grad_out, long long B, int C,
+                               long long S, int probas, const void *workspace, float *grad, void *stream);
+
 /* ---- KITTI frames: a LiDAR sweep, a calibration and 2-D boxes -> frustums (csrc/frames.hip; an additive group: the ABI version does not
  * move).  The reference reads prepared pickles and has no code for this stage; THIS is its definition, restated in numpy by
  * tests/frames_truth.py.  All geometry is fp64, one rounding per operation, sums left to right; a comparison with NaN is false.

@@ -179,6 +179,12 @@ SIGNATURES = {
     'pvcnn_dml_pair_partials': (_i, [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _ll, _i, _ll, _ll, _vp, _vp]),
     'pvcnn_dml_pair_finalize': (_i, [_ll, _i, _ll, _vp, _vp, _vp, _vp]),
     'pvcnn_dml_pair_bwd': (_i, [_vp, _ll, _vp, _ll, _vp, _ll, _vp, _vp, _ll, _i, _ll, _ll, _i, _vp, _vp, _vp]),
+    # the Lovasz-Softmax criterion (csrc/lovasz.hip): probabilities, one sorted list per (cloud, class), finalize; one backward
+    'pvcnn_lovasz_workspace_bytes': (_sz, [_ll, _i, _ll]),
+    'pvcnn_lovasz_probs': (_i, [_vp, _ll, _ll, _i, _ll, _vp, _vp]),
+    'pvcnn_lovasz_sort': (_i, [_vp, _ll, _vp, _ll, _ll, _i, _ll, _ll, _i, _vp, _vp, _vp]),
+    'pvcnn_lovasz_finalize': (_i, [_ll, _i, _ll, _i, _vp, _vp, _vp, _vp]),
+    'pvcnn_lovasz_bwd': (_i, [_vp, _ll, _vp, _vp, _ll, _i, _ll, _i, _vp, _vp, _vp]),
     # KITTI frames (csrc/frames.hip): scan + calibration + 2-D boxes -> frustums
     'pvcnn_frame_tiles': (_ll, [_ll]),
     'pvcnn_frame_project': (_i, [_vp, _ll, _ll, _vp, _vp, _d, _d, _d, _vp, _vp, _vp, _vp]),

@@ -1,17 +1,18 @@
 """huber_loss (reference: modules/functional/loss.py:13-17; plain torch, tiny tensors) and the criteria of the segmentation recipes
 on the device: cross_entropy (nn.CrossEntropyLoss on (B, classes, N) logits) on csrc/xent.hip, two launches forward and one backward
 where torch takes five to six; kl_loss (reference: modules/functional/loss.py:7-10) and dml_pair_loss, the four terms of a
-deep-mutual-learning step, on csrc/dml.hip."""
+deep-mutual-learning step, on csrc/dml.hip; lovasz_softmax, the IoU surrogate of Berman et al. (CVPR 2018) per cloud, on csrc/lovasz.hip."""
 import os
 
 import torch
 import torch.nn.functional as tf
 
 __all__ = ['kl_loss', 'kl_loss_is_fused', 'huber_loss', 'cross_entropy', 'cross_entropy_is_fused', 'dml_pair_loss',
-           'dml_pair_loss_is_fused']
+           'dml_pair_loss_is_fused', 'lovasz_softmax', 'lovasz_softmax_is_fused', 'lovasz_softmax_parts']
 
 fused_enabled = os.environ.get('PVCNN_FUSED_XENT', '1') != '0'      # (debug / A-B switch: 0 = torch's cross_entropy everywhere)
 dml_enabled = os.environ.get('PVCNN_FUSED_DML', '1') != '0'         # (0 = kl_loss as torch ops, dml_pair_loss composed of its terms)
+lovasz_enabled = os.environ.get('PVCNN_FUSED_LOVASZ', '1') != '0'   # (0 = lovasz_softmax as its torch composition everywhere)
 
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 
@@ -299,3 +300,186 @@ def _dml_pair_loss(outputs, outputs_student, targets, weight, ignore_index, redu
         with torch.no_grad():
             shared = _PairForward(a.detach(), b.detach(), targets.flatten(1), weight, ignore_index, bad_targets)
         return _DmlPairSide.apply(a, shared, 0), _DmlPairSide.apply(b, shared, 1)
+
+
+# ---- Lovasz-Softmax (Berman et al., CVPR 2018).  The definition is stated once, in include/pvcnn_hip.h; tests/lovasz_truth.py
+# restates it in numpy.
+
+_LOVASZ_CLASSES = ('present', 'all')
+
+
+def _lovasz_workspace_bytes(b, c, s):
+    """pvcnn_lovasz_workspace_bytes: 0 for what the kernels refuse (a list longer than 16384 points, sizes they do not index)."""
+    return _native()[0].pvcnn_lovasz_workspace_bytes(b, c, s)
+
+
+def lovasz_softmax_is_fused(input, target, per_cloud=True):
+    """True when lovasz_softmax(input, target, per_cloud=per_cloud) runs on the HIP kernels: device logits or probabilities
+    (B, C, d1, ...) in fp32 / fp16 / bf16 with int64 class-index targets (B, d1, ...) on the same device, one list per cloud
+    (per_cloud, or a single cloud) of at most 16384 points, and PVCNN_FUSED_LOVASZ not 0.  Everything else is the torch composition of
+    the same definition."""
+    if not lovasz_enabled:
+        return False
+    if not getattr(input, 'is_cuda', False) or not hasattr(target, 'dtype'):
+        return False
+    if input.dtype not in _FLOATS or input.dim() < 3:
+        return False
+    if target.dtype != torch.int64 or target.device != input.device:
+        return False
+    if target.dim() != input.dim() - 1 or target.shape[0] != input.shape[0] or target.shape[1:] != input.shape[2:]:
+        return False
+    if input.numel() == 0 or not (per_cloud or input.shape[0] == 1):
+        return False
+    b, c = input.shape[:2]
+    return _lovasz_workspace_bytes(b, c, input.numel() // (b * c)) != 0
+
+
+def _lovasz_composition(p, target, classes_all, ignore_index):
+    """The definition as batched torch ops on probabilities p (B, C, S) and targets (B, S): one stable descending sort on detached
+    keys (dead points keyed below every error), gathers, one cumulative sum, the closed-form steps in fp64.  Returns the loss in
+    fp64; differentiable for p (the order and the steps are constants)."""
+    b, c, s = p.shape
+    live = (target != ignore_index) & (target >= 0) & (target < c)
+    fg = (target.unsqueeze(1) == torch.arange(c, device=p.device).view(1, c, 1)) & live.unsqueeze(1)
+    e = torch.where(fg, 1.0 - p, p)
+    keys = torch.where(live.unsqueeze(1), e.detach(), torch.full_like(e, float('-inf')))
+    order = torch.sort(keys, dim=2, descending=True, stable=True).indices
+    e_sorted, fg_sorted = torch.gather(e, 2, order), torch.gather(fg, 2, order)
+    n, big_g = live.sum(1).view(b, 1, 1), fg.sum(2).unsqueeze(2)
+    cf = torch.cumsum(fg_sorted, 2)
+    i = torch.arange(1, s + 1, device=p.device).view(1, 1, s)
+    inter, union = (big_g - cf).double(), (big_g + i - cf).double()
+    # (union == 1 at a background element: a list without foreground, its first element -- the step is 1, not 0 / 0)
+    background = torch.where(union == 1.0, torch.ones_like(union), inter / (union * (union - 1.0)).clamp_min(1.0))
+    step = torch.where(fg_sorted, 1.0 / union, background)
+    step = torch.where(i <= n, step, torch.zeros_like(step))
+    per_class = (e_sorted.double() * step).sum(2)
+    counted = (n.view(b, 1) > 0).expand(b, c) if classes_all else big_g.view(b, c) > 0
+    k = counted.sum(1)
+    cloud = torch.where(k > 0, (per_class * counted).sum(1) / k.clamp_min(1), torch.zeros_like(per_class[:, 0]))
+    return cloud.mean()
+
+
+def _lovasz_launches(x, target, ignore_index, classes_all, probas, bad_targets):
+    """The forward launches on (B, C, S) fp32 / (B, S) int64: (loss, p, grad_p, workspace, p's batch stride).  p: the probabilities
+    (x itself under probas); grad_p: d loss(b, c) / d p, the signed steps; the workspace holds the per-cloud scales 1 / (k_b B)."""
+    lib, _run, batch_strided_ok = _native()
+    x, target = _rows(x, batch_strided_ok), _rows(target, _target_rows_ok)
+    B, C, S = x.shape
+    nbytes = lib.pvcnn_lovasz_workspace_bytes(B, C, S)
+    if nbytes == 0:
+        raise RuntimeError(f'lovasz_softmax: {B} x {C} lists of {S} points are more than the kernels serve')
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    grad_p = torch.empty((B, C, S), dtype=torch.float32, device=x.device)
+    if probas:
+        p, pbs = x, _bstride(x, C * S)
+    else:
+        p, pbs = torch.empty((B, C, S), dtype=torch.float32, device=x.device), C * S
+        _run(lib.pvcnn_lovasz_probs, 'lovasz_probs', x, x, _bstride(x, C * S), B, C, S, p)
+    _run(lib.pvcnn_lovasz_sort, 'lovasz_sort', x, p, pbs, target, _bstride(target, S), B, C, S, ignore_index, classes_all, ws, grad_p)
+    _run(lib.pvcnn_lovasz_finalize, 'lovasz_finalize', x, B, C, S, classes_all, ws, loss, bad_targets)
+    return loss, p, grad_p, ws, pbs
+
+
+class _LovaszSoftmax(torch.autograd.Function):
+    """(logits or probabilities (B, C, S) fp32, targets (B, S) int64, ...) -> loss (0-dim).  Forward keeps the probabilities, the
+    signed steps and the per-cloud scales; backward reads them and the incoming gradient ON THE DEVICE and writes the whole gradient
+    in one launch."""
+
+    @staticmethod
+    def forward(ctx, x, target, ignore_index, classes_all, probas, bad_targets):
+        loss, p, grad_p, ws, pbs = _lovasz_launches(x, target, ignore_index, classes_all, probas, bad_targets)
+        ctx.save_for_backward(p, grad_p, ws)
+        ctx.args = (pbs,) + tuple(x.shape) + (probas,)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        lib, _run, _ = _native()
+        p, grad_p, ws = ctx.saved_tensors
+        pbs, B, C, S, probas = ctx.args
+        if g.dtype != torch.float32:
+            g = g.float()
+        grad = torch.empty((B, C, S), dtype=torch.float32, device=p.device)
+        _run(lib.pvcnn_lovasz_bwd, 'lovasz_bwd', p, p, pbs, grad_p, g, B, C, S, probas, ws, grad)
+        return grad, None, None, None, None, None
+
+
+def _lovasz_arguments(input, target, classes, ignore_index, bad_targets, fused):
+    if classes not in _LOVASZ_CLASSES:
+        raise ValueError(f"lovasz_softmax: classes must be 'present' or 'all', got {classes!r}")
+    if not isinstance(ignore_index, int):
+        raise TypeError('lovasz_softmax: ignore_index must be an int')
+    if input.dim() < 3 or target.dim() != input.dim() - 1 or target.shape[0] != input.shape[0] or target.shape[1:] != input.shape[2:]:
+        raise ValueError(f'lovasz_softmax: input (B, C, d1, ...) and target (B, d1, ...) expected, got {tuple(input.shape)} and '
+                         f'{tuple(target.shape)}')
+    if fused and bad_targets is not None and not (bad_targets.dtype == torch.int64 and bad_targets.dim() == 0
+                                                  and bad_targets.device == input.device):
+        raise ValueError("bad_targets must be a 0-dim int64 tensor on the input's device")
+
+
+def _composition_inputs(input, target, per_cloud, probas):
+    """(probabilities (B', C, S'), targets (B', S')) of the composition: fp32 (fp64 stays fp64), per_cloud=False as ONE list."""
+    x = input.flatten(2)
+    if x.dtype != torch.float64:
+        x = x.float()
+    p = x if probas else tf.softmax(x, dim=1)
+    t = target.flatten(1)
+    if not per_cloud and p.shape[0] > 1:
+        p, t = p.permute(1, 0, 2).reshape(1, p.shape[1], -1), t.reshape(1, -1)
+    return p, t
+
+
+def lovasz_softmax(input, target, *, classes='present', per_cloud=True, ignore_index=-100, probas=False, bad_targets=None):
+    """The Lovasz-Softmax loss of Berman et al. (CVPR 2018), the surrogate of the mean IoU the meters report, on logits (or, with
+    `probas`, probabilities) (B, C, d1, ...) and int64 targets (B, d1, ...).  Per cloud and class the points' errors are ranked and
+    weighted by the steps of the Jaccard index along the ranking; `classes`: 'present' averages over the classes a cloud holds, 'all'
+    over all C; `per_cloud` (Berman's per_image): the mean over the clouds' losses, False: the whole batch as one list.
+
+    Where lovasz_softmax_is_fused says so the loss and its gradient come from csrc/lovasz.hip: three launches forward, one backward,
+    no host synchronisation (capturable), the same bits for the same inputs; half / bf16 inputs are evaluated in fp32.  Everything
+    else (CPU tensors, per_cloud=False over several clouds, lists beyond 16384 points) is a batched torch composition of the same
+    definition, differentiable through autograd.
+
+    A target outside [0, C) that is not ignore_index is treated as ignored; on the fused path `bad_targets`, a 0-dim int64 tensor on
+    the input's device, is incremented by their number (see cross_entropy)."""
+    return _lovasz_softmax(input, target, classes, per_cloud, ignore_index, probas, bad_targets,
+                           lovasz_softmax_is_fused(input, target, per_cloud))
+
+
+def _lovasz_softmax(input, target, classes, per_cloud, ignore_index, probas, bad_targets, fused):
+    """lovasz_softmax for a caller that has asked lovasz_softmax_is_fused already (modules.LovaszSoftmax)."""
+    _lovasz_arguments(input, target, classes, ignore_index, bad_targets, fused)
+    if not fused:
+        p, t = _composition_inputs(input, target, per_cloud, probas)
+        return _lovasz_composition(p, t, classes == 'all', ignore_index).to(p.dtype)
+    x = input.flatten(2)
+    if x.dtype != torch.float32:
+        x = x.float()                                    # half / bf16: the criterion is evaluated in fp32
+    with torch.autocast(x.device.type, enabled=False):
+        return _LovaszSoftmax.apply(x, target.flatten(1), ignore_index, int(classes == 'all'), int(bool(probas)), bad_targets)
+
+
+def lovasz_softmax_parts(input, target, *, classes='present', per_cloud=True, ignore_index=-100, probas=False):
+    """A diagnostic seam for the tests: (loss, probabilities, grad_probabilities) of lovasz_softmax with these arguments, detached.
+    On the fused path these are the device tensors the autograd node keeps for backward -- the fp32 loss, the (B, C, S) probabilities
+    the lists were ranked on, and d loss / d probabilities = the kept signed steps times the kept per-cloud scale 1 / (k_b B), the
+    product backward forms.  On the composition path: its fp64 loss before the cast, its probabilities ((1, C, B S) for
+    per_cloud=False) and autograd's gradient for them."""
+    fused = lovasz_softmax_is_fused(input, target, per_cloud)
+    _lovasz_arguments(input, target, classes, ignore_index, None, fused)
+    if not fused:
+        p, t = _composition_inputs(input.detach(), target, per_cloud, probas)
+        p = p.detach().requires_grad_()
+        loss = _lovasz_composition(p, t, classes == 'all', ignore_index)
+        grad, = torch.autograd.grad(loss, p)
+        return loss.detach(), p.detach(), grad
+    x = input.detach().flatten(2)
+    if x.dtype != torch.float32:
+        x = x.float()
+    with torch.no_grad(), torch.autocast(x.device.type, enabled=False):
+        loss, p, steps, ws, _ = _lovasz_launches(x, target.flatten(1), ignore_index, int(classes == 'all'), int(bool(probas)), None)
+        scale = ws[:4 * x.shape[0]].view(torch.float32)
+        return loss, p, steps * scale.view(-1, 1, 1)

@@ -1,12 +1,13 @@
 """KLLoss module (reference: modules/loss.py:6-9; fused through F.kl_loss), CrossEntropyLoss, nn.CrossEntropyLoss on the fused
-criterion, and DMLPairLoss, the two losses of a deep-mutual-learning step from one pass over both networks' logits."""
+criterion, DMLPairLoss, the two losses of a deep-mutual-learning step from one pass over both networks' logits, LovaszSoftmax, the
+IoU surrogate of Berman et al. per cloud, and CrossEntropyLovasz, cross entropy + weight * Lovasz-Softmax on the same logits."""
 import torch
 import torch.nn as nn
 
 from . import functional as F
-from .functional.loss import _cross_entropy, _dml_pair_loss
+from .functional.loss import _cross_entropy, _dml_pair_loss, _lovasz_softmax
 
-__all__ = ['KLLoss', 'CrossEntropyLoss', 'DMLPairLoss']
+__all__ = ['KLLoss', 'CrossEntropyLoss', 'DMLPairLoss', 'LovaszSoftmax', 'CrossEntropyLovasz']
 
 
 class KLLoss(nn.Module):
@@ -77,3 +78,57 @@ class DMLPairLoss(nn.Module):
                 self.bad_targets = torch.zeros((), dtype=torch.int64, device=outputs.device)
             counter = self.bad_targets
         return _dml_pair_loss(outputs, outputs_student, targets, c.weight, c.ignore_index, c.reduction, c.label_smoothing, counter, fused)
+
+
+class LovaszSoftmax(nn.Module):
+    """F.lovasz_softmax as a criterion: forward(input (B, C, N) logits, target (B, N)) -> loss.  On device tensors, one list per
+    cloud of up to 16384 points, the loss and its gradient are four HIP launches; anything else is the torch composition.
+
+    `bad_targets`: as CrossEntropyLoss's -- a 0-dim int64 tensor created on the first fused call, the running number of targets
+    outside [0, C) that were not ignore_index (they are treated as ignored).  `count_bad_targets=False` keeps no counter (for a
+    criterion that is added to one which counts the same targets already)."""
+
+    def __init__(self, classes='present', per_cloud=True, ignore_index=-100, *, count_bad_targets=True):
+        super().__init__()
+        if classes not in ('present', 'all'):
+            raise ValueError(f"LovaszSoftmax: classes must be 'present' or 'all', got {classes!r}")
+        self.classes, self.per_cloud, self.ignore_index = classes, per_cloud, ignore_index
+        self.count_bad_targets = count_bad_targets
+        self.bad_targets = None
+
+    def extra_repr(self):
+        return f'classes={self.classes!r}, per_cloud={self.per_cloud}, ignore_index={self.ignore_index}'
+
+    def forward(self, input, target):
+        counter = None
+        fused = F.lovasz_softmax_is_fused(input, target, self.per_cloud)
+        if fused and self.count_bad_targets:
+            if self.bad_targets is None or self.bad_targets.device != input.device:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError('LovaszSoftmax: call the criterion once before capturing it (its bad_targets counter is '
+                                       'created on the first call; GraphedTrainStep\'s warm-up steps do that)')
+                self.bad_targets = torch.zeros((), dtype=torch.int64, device=input.device)
+            counter = self.bad_targets
+        return _lovasz_softmax(input, target, self.classes, self.per_cloud, self.ignore_index, False, counter, fused)
+
+
+class CrossEntropyLovasz(nn.Module):
+    """The form people train segmentation with: CrossEntropyLoss(**cross-entropy arguments)(input, target) +
+    lovasz_weight * LovaszSoftmax(classes, per_cloud, ignore_index)(input, target) on the same logits, composed of the two fused
+    criteria (seven launches forward and backward on the device, capturable).  The cross-entropy arguments are nn.CrossEntropyLoss's
+    (weight, ignore_index, reduction, label_smoothing); its ignore_index is the Lovasz term's too.
+
+    `bad_targets`: the cross-entropy term's counter (both terms skip the same out-of-range targets; they are counted once)."""
+
+    def __init__(self, lovasz_weight=1.0, classes='present', per_cloud=True, **cross_entropy_arguments):
+        super().__init__()
+        self.lovasz_weight = float(lovasz_weight)
+        self.cross_entropy = CrossEntropyLoss(**cross_entropy_arguments)
+        self.lovasz = LovaszSoftmax(classes, per_cloud, self.cross_entropy.ignore_index, count_bad_targets=False)
+
+    @property
+    def bad_targets(self):
+        return self.cross_entropy.bad_targets
+
+    def forward(self, input, target):
+        return self.cross_entropy(input, target) + self.lovasz_weight * self.lovasz(input, target)

@@ -17,7 +17,14 @@ One JSON line per measurement.
 The four terms of a deep-mutual-learning step (train_dml.py:125-137) at the recipe's shape, S3DIS B=16, C=13, N=4096, forward + both
 backwards: (a) as before csrc/dml.hip -- modules.CrossEntropyLoss twice plus the torch kl_loss twice, in a fresh child process started
 with PVCNN_FUSED_DML=0 -- against (b) modules.DMLPairLoss on the pair kernels in this process.  Both processes stay up and take their
-rounds in turn (a, b, a, b, ...), each round replayed from a captured graph and issued eagerly, with the launches per pass."""
+rounds in turn (a, b, a, b, ...), each round replayed from a captured graph and issued eagerly, with the launches per pass.
+
+    python tools/loss_bench.py --lovasz [--iters 200] [--steps 20] [--rounds 3] [--skip-step]
+
+The Lovasz-Softmax criterion (csrc/lovasz.hip) against the batched torch composition of the same definition -- what every call the
+kernels do not serve runs -- by the first method above (one process, alternating rounds, replayed and eager, launch counts) at the
+S3DIS (16, 13, 4096), PVCNN++ (8, 13, 8192) and ShapeNet (8, 50, 2048) shapes; then the cfg2 step replayed from its graph with
+modules.CrossEntropyLoss and with modules.CrossEntropyLovasz inside: what adding the IoU surrogate to the criterion costs a step."""
 import argparse
 import copy
 import json
@@ -36,6 +43,7 @@ from pvcnn_amd.modules.functional import backend as seam                # noqa: 
 
 SHAPES = [(16, 13, 4096), (8, 50, 2048), (32, 2, 1024)]
 ARMS = (('torch', tf.cross_entropy), ('fused', PF.cross_entropy))
+LOVASZ_SHAPES = [(16, 13, 4096), (8, 13, 8192), (8, 50, 2048)]
 
 
 def between_events(fn, n):
@@ -48,9 +56,9 @@ def between_events(fn, n):
     return start.elapsed_time(stop) / n
 
 
-def verdict(base, new):
+def verdict(base, new, name='torch'):
     spread = max(base) - min(base)
-    return {'torch_spread': round(spread, 4), 'gain_median': round(sorted(base)[len(base) // 2] - sorted(new)[len(new) // 2], 4),
+    return {f'{name}_spread': round(spread, 4), 'gain_median': round(sorted(base)[len(base) // 2] - sorted(new)[len(new) // 2], 4),
             'faster_in_every_round_by_more_than_the_spread': bool(min(base) - max(new) > spread)}
 
 
@@ -85,12 +93,21 @@ def native_calls(fn):
     return labels
 
 
-def criterion_alone(shape, args, dev):
+def lovasz_arms():
+    from pvcnn_amd.modules.functional import loss as criteria
+
+    def composition(x, y):
+        return criteria._lovasz_softmax(x, y, 'present', True, -100, False, None, False)
+    return (('composition', composition), ('fused', PF.lovasz_softmax))
+
+
+def criterion_alone(shape, args, dev, arms=ARMS, is_fused=PF.cross_entropy_is_fused):
+    ARMS, (base, new) = arms, (arms[0][0], arms[1][0])
     b, c, s = shape
     g = torch.Generator().manual_seed(0)
     x = (4.0 * torch.randn(b, c, s, generator=g)).to(dev).requires_grad_()
     y = torch.randint(0, c, (b, s), generator=g).to(dev)
-    assert PF.cross_entropy_is_fused(x, y)
+    assert is_fused(x, y)
 
     def once(fn):
         x.grad = None
@@ -120,16 +137,17 @@ def criterion_alone(shape, args, dev):
     out = {'measurement': 'criterion forward + backward', 'shape': list(shape), 'iters_per_round': args.iters, 'rounds': args.rounds,
            'device': torch.cuda.get_device_name(0), 'unit': 'us per forward + backward'}
     out.update({k: [round(v, 3) for v in vs] for k, vs in us.items()})
-    out['replay'] = verdict(us['torch_replay'], us['fused_replay'])
-    out['eager'] = verdict(us['torch_eager'], us['fused_eager'])
+    out['replay'] = verdict(us[f'{base}_replay'], us[f'{new}_replay'], base)
+    out['eager'] = verdict(us[f'{base}_eager'], us[f'{new}_eager'], base)
     for name, _ in ARMS:
         out[f'{name}_device_kernels'] = None if kernels[name] is None else len(kernels[name])
         out[f'{name}_device_kernel_names'] = None if kernels[name] is None else sorted(set(n[:60] for n in kernels[name]))
-    out['fused_native_calls'] = native_calls(lambda: once(PF.cross_entropy))
+    out[f'{new}_native_calls'] = native_calls(lambda: once(arms[1][1]))
     return out
 
 
-def replayed_step(args, dev):
+def replayed_step(args, dev, arms=ARMS):
+    ARMS, (base_arm, new_arm) = arms, (arms[0][0], arms[1][0])
     from pvcnn_amd.dp import GradBucketReducer
     from pvcnn_amd.graph import GraphedTrainStep
     from pvcnn_amd.optim import FlatAdam
@@ -151,8 +169,8 @@ def replayed_step(args, dev):
             losses[name] = steps[name].loss.item()
     out = {'measurement': 'cfg2 step replayed from its graph (PVCNN 1xC, B=16, N=4096, FlatAdam)', 'steps_per_round': args.steps,
            'rounds': args.rounds, 'device': torch.cuda.get_device_name(0), 'unit': 'ms per step',
-           'torch': [round(v, 4) for v in ms['torch']], 'fused': [round(v, 4) for v in ms['fused']], 'last_loss': losses}
-    out.update(verdict(ms['torch'], ms['fused']))
+           base_arm: [round(v, 4) for v in ms[base_arm]], new_arm: [round(v, 4) for v in ms[new_arm]], 'last_loss': losses}
+    out.update(verdict(ms[base_arm], ms[new_arm], base_arm))
     return out
 
 
@@ -252,6 +270,7 @@ def main():
     ap.add_argument('--dml', action='store_true', help='the deep-mutual-learning criterion pair only: composed (child process) against fused')
     ap.add_argument('--dml-iters', type=int, default=2000, help='DML forward + backward passes per round')
     ap.add_argument('--dml-child', action='store_true', help=argparse.SUPPRESS)
+    ap.add_argument('--lovasz', action='store_true', help='the Lovasz-Softmax criterion: the torch composition against the fused kernels')
     args = ap.parse_args()
     assert torch.cuda.is_available(), 'loss_bench needs a GPU'
     dev = torch.device('cuda:0')
@@ -259,6 +278,14 @@ def main():
         return dml_child(args, dev)
     if args.dml:
         print(json.dumps(dml_pair(args, dev)), flush=True)
+        return
+    if args.lovasz:
+        import pvcnn_amd.modules as M
+        for shape in LOVASZ_SHAPES:
+            print(json.dumps(criterion_alone(shape, args, dev, lovasz_arms(), PF.lovasz_softmax_is_fused)), flush=True)
+        if not args.skip_step:
+            print(json.dumps(replayed_step(args, dev, (('cross_entropy', M.CrossEntropyLoss()), ('cross_entropy_lovasz', M.CrossEntropyLovasz())))),
+                  flush=True)
         return
     for shape in SHAPES:
         print(json.dumps(criterion_alone(shape, args, dev)), flush=True)
