@@ -2,7 +2,10 @@
 
 There is no bit-exact bar here: the reference delegates this op to cuDNN, whose summation order
 is unspecified (parity unpinned at that boundary; oracle = the same torch op).
-Tolerance: fp32 round-off for K = 27*Ci terms -- 1e-5 relative to the tensor's scale, stated here."""
+Tolerance: fp32 round-off for K = 27*Ci terms -- 1e-5 relative to the tensor's scale, stated here.
+
+Bit-exact bars where the operands admit them (one non-zero product per output element), the plain-bf16 launches against fp64 on
+bf16-rounded operands at TOL, and every instantiation of csrc/route.h: tests/test_gpu_products_exact.py."""
 import pytest
 import torch
 import torch.nn.functional as F

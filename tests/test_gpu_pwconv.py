@@ -1,7 +1,10 @@
 """1x1 convolutions of SharedMLP on the MFMA GEMM kernels (csrc/pointwise.hip) vs an fp64 evaluation.
 
 Reference call sites: modules/shared_mlp.py:9-25 (nn.Conv1d / nn.Conv2d, kernel 1).  Tolerance: fp32
-round-off of a K-term dot product, 1e-5 relative to the largest magnitude of the result."""
+round-off of a K-term dot product, 1e-5 relative to the largest magnitude of the result.
+
+Bit-exact bars where the operands admit them (one non-zero product per output element), the plain-bf16 launches -- backward-data
+included -- against fp64 on bf16-rounded operands at 1e-5, and every instantiation of csrc/route.h: tests/test_gpu_products_exact.py."""
 import pytest
 import torch
 import torch.nn as nn
