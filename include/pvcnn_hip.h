@@ -1221,6 +1221,66 @@ PVCNN_API int pvcnn_shape_normals(const float *rows, long long R, int ld, const 
 PVCNN_API int pvcnn_cloud_centroids(const float *rows, long long R, int ld, const int64_t *offsets, long long W, float *out,
                                     void *stream);
 
+/* ---- Sparse voxels: the submanifold sparse 3x3x3 convolution on the occupied voxels of a cloud (csrc/sparse.hip,
+ * pvcnn_amd/modules/functional/sparse.py; an additive group: the ABI version does not move).  A dense Conv3d forms an output at every
+ * voxel of the grid; this operator is defined on the ACTIVE voxels only -- those that hold at least one point -- which is the
+ * convolution of SPVCNN.  THIS is the definition, restated in torch fp64 by tests/sparse_conv_truth.py.
+ *
+ * The map, from cnt (B, R^3) int32 (what voxelization already has), built once per (coordinates, R).  A voxel is active when
+ * cnt > 0.  With `cap` the static capacity in rows, chosen by the caller, and count = min(active voxels, cap):
+ *   voxel   (cap)     int32  the flat voxel number b R^3 + (x R + y) R + z of row j < count, ascending: the rows of one cloud are
+ *                            consecutive, neighbours in z are adjacent rows; -1 for j >= count.
+ *   index   (B R^3)   int32  the row of a voxel, or -1 (inactive, or dropped because cap was too small).
+ *   offsets (B + 1)   int32  the first row of every cloud, clamped to cap; offsets[B] IS the device word `count` that every other
+ *                            entry point takes.  The count never visits the host: every launch is sized by cap and bounded by this
+ *                            word, so the group can be captured in a graph and replayed on another occupancy.
+ *   nbr     (cap, 27) int32  the row of each of the 27 neighbours of row j, in nn.Conv3d's tap order (dx, dy, dz), tap = 9 (dx + 1) +
+ *                            3 (dy + 1) + (dz + 1); tap 13 is j itself; -1 for a neighbour that is inactive, outside [0, R) in any
+ *                            axis (never a voxel of another cloud or of the next z row), and everywhere for j >= count.
+ *   overflow (1)      int32  1 when more than cap voxels are active -- the map then keeps the first cap of them and nothing is written
+ *                            out of bounds -- else 0.
+ * Supported: 1 <= R <= PVCNN_SPARSE_MAX_R, B R^3 < 2^31, 1 <= cap < 2^31 / 27; the size queries return 0 outside that range.  Four
+ * launches (count per chunk, scan, fill, table), no atomics: deterministic.
+ *
+ * pvcnn_sparse_gather: grid (B, C, R^3) fp32 -> rows (cap, C) fp32, row-major (a voxel's channels are contiguous); rows >= count are
+ *   written as zeros.  pvcnn_sparse_scatter: rows -> grid, zero at every voxel without a row; every word of the grid is written.  Each
+ *   is the other's backward.
+ *
+ * The convolution, weight (Co, Ci, 3, 3, 3) as nn.Conv3d holds it:
+ *   y[j, co] = bias[co] + sum_tap sum_ci W[co, ci, tap] x[nbr[j, tap], ci]      j < count; nbr = -1 contributes nothing
+ *   y[j, :]  = 0                                                                j >= count (no bias there)
+ *   = F.conv3d(padding = 1) of the zero-filled dense grid, read at the active voxels.  No row >= count of x is ever read.
+ *   Arithmetic: v_mfma_f32_32x32x2_f32, exact fp32 operands, fp32 accumulation in the order (tap, ci) ascending -- the `fp32` math
+ *   mode of csrc/conv3d.hip.  A tile of PVCNN_SPARSE_ROW_TILE rows leaves out a tap at which none of its rows has a neighbour: only
+ *   products with an exact zero, the same bits (pvcnn_sparse_debug_skip(0) keeps them in; -1 only asks; returns the previous state).
+ *   pvcnn_sparse_conv3d_weight_transform: W -> the image `wt` pvcnn_sparse_conv3d_fwd takes, (27, Ci, Co); for_bwd_data: (27, Co, Ci)
+ *   with the taps reversed, on which the same entry point (Ci and Co exchanged, no bias, grad_y for x) is backward-data
+ *   grad_x[i, ci] = sum_tap sum_co W[co, ci, tap] grad_y[nbr[i, 26 - tap], co].
+ *   pvcnn_sparse_conv3d_bwd_weight: grad_w[co, ci, tap] = sum_j grad_y[j, co] x[nbr[j, tap], ci] and grad_bias[co] = sum_{j < count}
+ *   grad_y[j, co] (either may be NULL): partial sums over chunks of PVCNN_SPARSE_WGRAD_CHUNK rows in `workspace` (16-byte aligned),
+ *   added in ascending chunk order by a second launch.  No float atomics: every result of the group is the same bits on every run.
+ *
+ * Plain launches on `stream`: no allocation, no synchronisation. */
+#define PVCNN_SPARSE_MAX_R 128
+#define PVCNN_SPARSE_ROW_TILE 64
+#define PVCNN_SPARSE_WGRAD_CHUNK 1024
+PVCNN_API size_t pvcnn_sparse_map_workspace_bytes(int B, int R);
+PVCNN_API size_t pvcnn_sparse_map_bytes(int B, int R, long long cap);
+PVCNN_API int pvcnn_sparse_map(const int32_t *cnt, int B, int R, long long cap, int32_t *voxel, int32_t *index, int32_t *offsets,
+                               int32_t *nbr, int32_t *overflow, void *workspace, size_t workspace_bytes, void *stream);
+PVCNN_API int pvcnn_sparse_gather(const float *grid, const int32_t *voxel, const int32_t *count, int B, int C, int R, long long cap,
+                                  float *rows, void *stream);
+PVCNN_API int pvcnn_sparse_scatter(const float *rows, const int32_t *index, const int32_t *count, int B, int C, int R, long long cap,
+                                   float *grid, void *stream);
+PVCNN_API int pvcnn_sparse_conv3d_weight_transform(const float *w, int Co, int Ci, int for_bwd_data, float *wt, void *stream);
+PVCNN_API int pvcnn_sparse_conv3d_fwd(const float *x, const float *wt, const float *bias, const int32_t *nbr, const int32_t *count,
+                                      long long cap, int Ci, int Co, float *y, void *stream);
+PVCNN_API size_t pvcnn_sparse_conv3d_bwd_weight_workspace_bytes(long long cap, int Ci, int Co);
+PVCNN_API int pvcnn_sparse_conv3d_bwd_weight(const float *x, const float *grad_y, const int32_t *nbr, const int32_t *count,
+                                             long long cap, int Ci, int Co, float *grad_w, float *grad_bias, void *workspace,
+                                             size_t workspace_bytes, void *stream);
+PVCNN_API int pvcnn_sparse_debug_skip(int on);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,17 @@ SIGNATURES = {
     'pvcnn_k_nearest': (_i, [_vp, _ll, _i, _vp, _ll, _i, _vp, _vp]),
     'pvcnn_shape_normals': (_i, [_vp, _ll, _i, _vp, _ll, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     'pvcnn_cloud_centroids': (_i, [_vp, _ll, _i, _vp, _ll, _vp, _vp]),
+    # sparse voxels (csrc/sparse.hip): the map of the active voxels, rows in and out of dense grids, the submanifold 3x3x3 convolution
+    'pvcnn_sparse_map_workspace_bytes': (_sz, [_i, _i]),
+    'pvcnn_sparse_map_bytes': (_sz, [_i, _i, _ll]),
+    'pvcnn_sparse_map': (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'pvcnn_sparse_gather': (_i, [_vp, _vp, _vp, _i, _i, _i, _ll, _vp, _vp]),
+    'pvcnn_sparse_scatter': (_i, [_vp, _vp, _vp, _i, _i, _i, _ll, _vp, _vp]),
+    'pvcnn_sparse_conv3d_weight_transform': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'pvcnn_sparse_conv3d_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp]),
+    'pvcnn_sparse_conv3d_bwd_weight_workspace_bytes': (_sz, [_ll, _i, _i]),
+    'pvcnn_sparse_conv3d_bwd_weight': (_i, [_vp, _vp, _vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'pvcnn_sparse_debug_skip': (_i, [_i]),
 }
 
 _lib = None

@@ -1677,6 +1677,114 @@ class HipBackend:
         _run(self.lib.pvcnn_cloud_centroids, 'cloud_centroids', rows, rows, r, ld, offsets, w, out)
         return out
 
+    # ---- sparse voxels (csrc/sparse.hip; include/pvcnn_hip.h "Sparse voxels"; functional/sparse.py owns the autograd nodes) ----
+    has_sparse = True
+    SPARSE_ROW_TILE = 64
+    SPARSE_MAX_R = 128
+
+    def sparse_supported(self, b, r):
+        """True when a (b, r^3) grid has a map: r <= 128 and b r^3 < 2^31 (the size query's answer)."""
+        return self.lib.pvcnn_sparse_map_workspace_bytes(int(b), int(r)) > 0
+
+    def sparse_skip(self, on=None):
+        """The debug switch of the tap skip (on by default): set it (True / False) or only ask (None); -> the previous state."""
+        return bool(self.lib.pvcnn_sparse_debug_skip(-1 if on is None else int(bool(on))))
+
+    def sparse_map(self, cnt, resolution, cap, out=None):
+        """cnt (B, R^3) int32 -> (voxel (cap,), index (B R^3,), offsets (B + 1,), nbr (cap, 27), overflow (1,)), all int32; four
+        launches, nothing read back.  `out=`: the five tensors, preallocated (static buffers of a captured step)."""
+        _i32(cnt, 'cnt')
+        r, cap = int(resolution), int(cap)
+        _arg(cnt.dim() == 2 and cnt.shape[1] == r ** 3, 'sparse_map: cnt (B, R^3) int32 expected')
+        b = cnt.shape[0]
+        nbytes = self.lib.pvcnn_sparse_map_workspace_bytes(b, r)
+        _arg(nbytes > 0 and self.lib.pvcnn_sparse_map_bytes(b, r, cap) > 0,
+             'sparse_map: R <= 128, B R^3 < 2^31 and 1 <= cap < 2^31 / 27 expected')
+        dev = cnt.device
+        shapes = ((cap,), (b * r ** 3,), (b + 1,), (cap, 27), (1,))
+        if out is None:
+            out = tuple(torch.empty(s, dtype=torch.int32, device=dev) for s in shapes)
+        else:
+            _arg(len(out) == 5, 'sparse_map: out= (voxel, index, offsets, nbr, overflow) expected')
+            out = tuple(self._shapes_out(o, s, torch.int32, dev, 'sparse_map') for o, s in zip(out, shapes))
+        workspace = self._scratch(nbytes, dev)
+        _run(self.lib.pvcnn_sparse_map, 'sparse_map', cnt, cnt, b, r, cap, *out, workspace, workspace.numel())
+        return out
+
+    @staticmethod
+    def _sparse_count(count, ref, who):
+        _i32(count, 'count')
+        _arg(count.numel() == 1 and count.device == ref.device, f'{who}: count = one int32 word on the device expected')
+
+    def sparse_gather(self, grid, voxel, count, out=None):
+        """grid (B, C, R^3) fp32 -> rows (cap, C) fp32, zeros at the rows >= count.  One launch."""
+        _f32(grid, 'grid'); _i32(voxel, 'voxel'); self._sparse_count(count, grid, 'sparse_gather')
+        _arg(grid.dim() == 3 and voxel.dim() == 1 and voxel.device == grid.device, 'sparse_gather: grid (B, C, R^3), voxel (cap,) expected')
+        b, c, r3 = grid.shape
+        r = round(r3 ** (1.0 / 3.0))
+        _arg(r ** 3 == r3, 'sparse_gather: a cubic grid expected')
+        cap = voxel.shape[0]
+        rows = self._shapes_out(out, (cap, c), torch.float32, grid.device, 'sparse_gather')
+        _run(self.lib.pvcnn_sparse_gather, 'sparse_gather', grid, grid, voxel, count, b, c, r, cap, rows)
+        return rows
+
+    def sparse_scatter(self, rows, index, count, batch, resolution, out=None):
+        """rows (cap, C) fp32 -> grid (B, C, R^3) fp32, zero at every voxel without a row; every word is written.  One launch."""
+        _f32(rows, 'rows'); _i32(index, 'index'); self._sparse_count(count, rows, 'sparse_scatter')
+        b, r = int(batch), int(resolution)
+        _arg(rows.dim() == 2 and index.dim() == 1 and index.shape[0] == b * r ** 3 and index.device == rows.device,
+             'sparse_scatter: rows (cap, C), index (B R^3,) expected')
+        cap, c = rows.shape
+        grid = self._shapes_out(out, (b, c, r ** 3), torch.float32, rows.device, 'sparse_scatter')
+        _run(self.lib.pvcnn_sparse_scatter, 'sparse_scatter', rows, rows, index, count, b, c, r, cap, grid)
+        return grid
+
+    def sparse_conv3d_weight_image(self, weight, for_bwd_data=False):
+        """weight (Co, Ci, 3, 3, 3) -> the image the convolution kernel reads: (27, Ci, Co), or for backward-data (27, Co, Ci) with
+        the taps reversed.  One launch."""
+        _f32(weight, 'weight')
+        _arg(weight.dim() == 5 and tuple(weight.shape[2:]) == (3, 3, 3), 'sparse_conv3d: weight (Co, Ci, 3, 3, 3) expected')
+        co, ci = weight.shape[:2]
+        wt = torch.empty((27, co, ci) if for_bwd_data else (27, ci, co), dtype=torch.float32, device=weight.device)
+        _run(self.lib.pvcnn_sparse_conv3d_weight_transform, 'sparse_conv3d_weight_transform', weight, weight, co, ci, int(bool(for_bwd_data)), wt)
+        return wt
+
+    def sparse_conv3d_forward(self, rows, wt, bias, nbr, count, out=None):
+        """rows (cap, Ci), wt (27, Ci, Co) (sparse_conv3d_weight_image), bias (Co,) or None -> (cap, Co); zeros at the rows >= count.
+        Backward-data is the same call on grad_y and the backward image, without a bias.  One launch."""
+        _f32(rows, 'rows'); _f32(wt, 'wt'); _i32(nbr, 'nbr'); self._sparse_count(count, rows, 'sparse_conv3d')
+        _arg(rows.dim() == 2 and wt.dim() == 3 and wt.shape[0] == 27 and wt.shape[1] == rows.shape[1] and wt.device == rows.device,
+             'sparse_conv3d: rows (cap, Ci) and a weight image (27, Ci, Co) expected')
+        cap, ci = rows.shape
+        co = wt.shape[2]
+        _arg(tuple(nbr.shape) == (cap, 27) and nbr.device == rows.device, 'sparse_conv3d: nbr (cap, 27) int32 expected')
+        if bias is not None:
+            _f32(bias, 'bias')
+            _arg(tuple(bias.shape) == (co,) and bias.device == rows.device, 'sparse_conv3d: bias (Co,) expected')
+        y = self._shapes_out(out, (cap, co), torch.float32, rows.device, 'sparse_conv3d')
+        _run(self.lib.pvcnn_sparse_conv3d_fwd, 'sparse_conv3d_fwd', rows, rows, wt, bias, nbr, count, cap, ci, co, y)
+        return y
+
+    def sparse_conv3d_backward_weight(self, rows, grad_y, nbr, count, want_weight=True, want_bias=True, out=None, out_bias=None):
+        """-> (grad_w (Co, Ci, 3, 3, 3) or None, grad_bias (Co,) or None): partial sums per chunk of rows, added in a fixed order by a
+        second launch (no float atomics)."""
+        _f32(rows, 'rows'); _f32(grad_y, 'grad_y'); _i32(nbr, 'nbr'); self._sparse_count(count, rows, 'sparse_conv3d_bwd_weight')
+        _arg(rows.dim() == 2 and grad_y.dim() == 2 and grad_y.shape[0] == rows.shape[0] and grad_y.device == rows.device,
+             'sparse_conv3d_bwd_weight: rows (cap, Ci), grad_y (cap, Co) expected')
+        cap, ci = rows.shape
+        co = grad_y.shape[1]
+        _arg(tuple(nbr.shape) == (cap, 27) and nbr.device == rows.device, 'sparse_conv3d_bwd_weight: nbr (cap, 27) int32 expected')
+        gw = self._shapes_out(out, (co, ci, 3, 3, 3), torch.float32, rows.device, 'sparse_conv3d_bwd_weight') if want_weight else None
+        gb = self._shapes_out(out_bias, (co,), torch.float32, rows.device, 'sparse_conv3d_bwd_weight') if want_bias else None
+        if gw is None and gb is None:
+            return None, None
+        nbytes = self.lib.pvcnn_sparse_conv3d_bwd_weight_workspace_bytes(cap, ci, co)
+        _arg(nbytes > 0, 'sparse_conv3d_bwd_weight: sizes out of range')
+        workspace = self._scratch(nbytes, rows.device)
+        _run(self.lib.pvcnn_sparse_conv3d_bwd_weight, 'sparse_conv3d_bwd_weight', rows, rows, grad_y, nbr, count, cap, ci, co, gw, gb,
+             workspace, workspace.numel())
+        return gw, gb
+
 
 class _WeightBank:
     """Persistent f16x2 image pairs of registered weights (HipBackend.weight_bank_*).  An entry is keyed by (kind, data pointer,
